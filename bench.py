@@ -2,6 +2,7 @@
 """Throughput benchmark of the DWC-GAN training hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--config c1|c2|c3|c4] [--scaling weak|strong] [--ledger out.json]
+                    [--dump-outputs DIR] [--full]
 
 N > 1: either launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or
 plainly as ``python bench.py --gpus N``: the parent then starts N rank processes itself BEFORE anything touches a GPU
@@ -17,13 +18,20 @@ HBM.  Workloads (BASELINE.json ``configs``; weak scaling — the per-GPU batch i
     c4  configs[4]  256x256, 8 per GPU, fp32 (global batch 64 on 8 GPUs)
 
 ``--scaling strong`` fixes the GLOBAL batch at the configuration's 8-GPU value (c1 128, c2 1024, c3 512, c4 64; or
-``--global-batch``) and gives every rank 1/N of it.  With N > 1 the record also carries BASELINE's own multi-GPU
-configurations, c3 (configs[3]) and c4 (configs[4]), as legs under "also" (N == 1: c2).
+``--global-batch``) and gives every rank 1/N of it.  With ``--full`` and N > 1 the record also carries BASELINE's own
+multi-GPU configurations, c3 (configs[3]) and c4 (configs[4]), as legs under "also" (N == 1: c2).
 
-Rank 0 prints ONE JSON line with the metric, the live roofline figure of the SINGLE kernel that owns the largest share of
-the instrumented step (HIP events on the launch stream around every conv launch of the last timed step; executed flops
-over that kernel's own dense peak) and, for N == 1, the CPU baseline (the oracle timed on the host cores by BASELINE.md
-section 3's protocol).
+Rank 0 prints ONE JSON line.  A plain run measures the headline workload only: set-up, `--warmup` untimed steps, `--steps`
+timed steps, and the record with the metric, `ms_per_step` and the losses of the last step.  ``--full`` adds everything
+else: the live roofline figure of the SINGLE kernel that owns the largest share of the instrumented step (HIP events on
+the launch stream around every conv launch of the last timed step; executed flops over that kernel's own dense peak), the
+per-kernel table, the legs under "also" and, for N == 1, the CPU baseline (the oracle timed on the host cores by
+BASELINE.md section 3's protocol).
+
+``--dump-outputs DIR`` writes what the last timed step computed, after the timing, as float32 / float64 .npy files: every
+loss of the step (``loss_<name>.npy``) and a fixed, seeded sample of the updated G / D weights and of their moving
+averages (``<net>_state.npy``).  The inputs (weights, batches, random streams) are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import glob
@@ -202,6 +210,30 @@ def run_iteration(trainer, batch, cfg, it):
     trainer.update_attention_status(it)
 
 
+DUMP_NETS = ("gen", "dis", "gen_copy", "dis_copy")   # the updated weights and their moving averages
+DUMP_SAMPLE = 1 << 21                                 # elements kept per network (4 x 8 MB, far below the 64 MB cap)
+
+
+def dump_outputs(trainer, out_dir):
+    """What the last step computed, as a caller of the training step receives it: every loss (``loss_<name>.npy``, float64)
+    and each network's floating-point state_dict entries, flattened and concatenated in state_dict order (``<net>_state.npy``,
+    float32), as a fixed seeded sample of DUMP_SAMPLE elements when the network holds more (the same positions every run)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in sorted(vars(trainer).items()):
+        if name.startswith("loss_") and isinstance(v, (torch.Tensor, float, int)) and not isinstance(v, bool):
+            val = v.detach().double().cpu().numpy().reshape(-1) if isinstance(v, torch.Tensor) else np.array([v], dtype=np.float64)
+            np.save(os.path.join(out_dir, name + ".npy"), val)
+    for net in DUMP_NETS:
+        sd = getattr(trainer, net).state_dict()
+        flat = torch.cat([t.detach().reshape(-1).float() for t in sd.values() if t.is_floating_point()]).cpu().numpy()
+        if flat.size > DUMP_SAMPLE:
+            flat = flat[np.sort(np.random.default_rng(1234).choice(flat.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(out_dir, net + "_state.npy"), flat)
+
+
 def cpu_baseline(gen_sd, dis_sd, cfg, image_size, batch, warmup, timed, thread_counts):
     """The CPU oracle (as_written: with the work the reference also does and discards) on the host cores, by the protocol of
     BASELINE.md section 3 / SURVEY.md 8(d): same synthetic inputs and shapes as the GPU workload's parity configuration
@@ -364,10 +396,12 @@ def spawn_ranks(args, timeout_s=3600):
     return rc
 
 
-def measure(args, config_name, steps, warmup, dev, dist, rank, world, force_dp):
+def measure(args, config_name, steps, warmup, dev, dist, rank, world, force_dp, instrument=True, dump_dir=None, keep_init=False):
     """One workload: build the trainer, `warmup` untimed + `steps` timed full iterations between barriers / device
-    synchronisations (MAX over ranks), HIP-event spans of the conv launches of the last timed step.  Returns
-    (record dict on rank 0 else None, initial G / D state dicts for the CPU baseline)."""
+    synchronisations (MAX over ranks); with `instrument`, HIP-event spans of the conv launches of the last timed step and
+    the roofline / per-kernel figures built from them; with `dump_dir`, the last step's outputs written there (rank 0,
+    after the timing).  Returns (record dict on rank 0 else None, initial G / D state dicts for the CPU baseline when
+    `keep_init` else None)."""
     import contextlib
     import io
 
@@ -406,8 +440,10 @@ def measure(args, config_name, steps, warmup, dev, dist, rank, world, force_dp):
         dp.broadcast_module(trainer.dis)
         trainer.copy_nets()
         trainer.enable_data_parallel()                       # flat gradient buckets, all-reduce overlapped with backward
-    init_gen = {k: v.detach().cpu().clone() for k, v in trainer.gen.state_dict().items()}
-    init_dis = {k: v.detach().cpu().clone() for k, v in trainer.dis.state_dict().items()}
+    init_sd = None
+    if keep_init:
+        init_sd = ({k: v.detach().cpu().clone() for k, v in trainer.gen.state_dict().items()},
+                   {k: v.detach().cpu().clone() for k, v in trainer.dis.state_dict().items()})
 
     # fresh batch per iteration, pre-generated on the device (4 distinct, cycled)
     batches = [synth.make_batch(per_gpu_batch, image_size, seed=1000 * rank + i, device=dev) for i in range(4)]
@@ -427,7 +463,7 @@ def measure(args, config_name, steps, warmup, dev, dist, rank, world, force_dp):
     sync()
     t0 = time.perf_counter()
     for s in range(steps):
-        if s == steps - 1:
+        if instrument and s == steps - 1:
             ops.TIMER = ops.KernelTimer()                    # HIP events around the conv launches of the last timed step
         run_iteration(trainer, batches[it % 4], cfg, it)
         it += 1
@@ -440,10 +476,31 @@ def measure(args, config_name, steps, warmup, dev, dist, rank, world, force_dp):
         elapsed = float(t.item())
     if rank != 0:
         return None, None
+    if dump_dir:
+        dump_outputs(trainer, dump_dir)
 
     images = per_gpu_batch * world * steps
     value = images / elapsed
-    spans = timer.summary() if timer is not None else {}
+    out = {
+        "metric": "CelebA %dx%d training images/sec" % (image_size, image_size), "value": round(value, 3), "unit": "images/s",
+        "n_gpus": world, "steps": steps, "warmup": warmup,
+        "ms_per_step": round(elapsed / steps * 1e3, 3), "higher_is_better": True, "scaling": args.scaling,
+        "vs_baseline": None, "dtype": "bf16" if precision == "bf16" else "f32", "data": "synthetic",
+        "config": {"workload": "%s, full iteration (dis_update + gen_update + EMA + LR step), vgg_w=%g%s" % (
+                       conf["label"], args.vgg_w,
+                       workload_note(ops, precision)),
+                   "name": config_name, "image_size": image_size, "per_gpu_batch": per_gpu_batch,
+                   "global_batch": per_gpu_batch * world, "parallelism": "dp%d" % world},
+        "loss_dis_all": round(float(trainer.loss_dis_all.detach()), 5),
+        "loss_gen_total": round(float(trainer.loss_gen_total.detach()), 5),
+    }
+    if getattr(trainer, "_reducers", None):
+        out["data_parallel"] = {k: {"buckets": len(r.buckets), "bucket_mb": [round(b["flat"].numel() * 4 / 2 ** 20, 1) for b in r.buckets],
+                                    "all_reduces": r.calls, "launched_from_inside_backward": r.launched_early}
+                                for k, r in trainer._reducers.items()}
+    if timer is None:
+        return out, init_sd
+    spans = timer.summary()
 
     def total(pred):
         ent = {"launches": 0, "ms": 0.0, "flops": 0.0, "exec_flops": 0.0}
@@ -491,13 +548,13 @@ def measure(args, config_name, steps, warmup, dev, dist, rank, world, force_dp):
             out["products_per_mac"] = round(ex_all["exec_flops"] / max(ex_all["flops"], 1.0), 2)
         return out
 
-    ledger = timer.ledger() if timer is not None else {}
+    ledger = timer.ledger()
     table = kernel_table(ledger, precision, split_generic=True)
     if getattr(args, "ledger", None):
         with open(args.ledger if config_name == args.config else args.ledger + "." + config_name, "w") as f:
             json.dump({"config": config_name, "precision": precision, "per_gpu_batch": per_gpu_batch, "image_size": image_size,
                        "ledger": ledger, "kernels": kernel_table(ledger, precision),
-                       "hbm_ops": timer.hbm_ledger() if timer is not None else {}}, f, indent=1)
+                       "hbm_ops": timer.hbm_ledger()}, f, indent=1)
     dom = total(lambda t: t.endswith(DOMINANT))
     x3 = total(lambda t: t.endswith(X3))
     # the generator decode conv stack (8 AdaIN-ResBlock 3x3 convs, two 5x5 upsampling convs, fused heads)
@@ -557,16 +614,7 @@ def measure(args, config_name, steps, warmup, dev, dist, rank, world, force_dp):
                    "algorithmic_gflop_per_launch": round(x3["flops"] / x3["launches"] / 1e9, 3)}
     step_flops = sum(v["flops"] for v in spans.values())            # conv + linear-as-conv launches of ONE step, this rank
     step_tflops = step_flops * world / (elapsed / steps) / 1e12
-    out = {
-        "metric": "CelebA %dx%d training images/sec" % (image_size, image_size), "value": round(value, 3), "unit": "images/s",
-        "n_gpus": world, "steps": steps, "warmup": warmup,
-        "ms_per_step": round(elapsed / steps * 1e3, 3), "higher_is_better": True, "scaling": args.scaling,
-        "vs_baseline": None, "dtype": "bf16" if precision == "bf16" else "f32", "data": "synthetic",
-        "config": {"workload": "%s, full iteration (dis_update + gen_update + EMA + LR step), vgg_w=%g%s" % (
-                       conf["label"], args.vgg_w,
-                       workload_note(ops, precision)),
-                   "name": config_name, "image_size": image_size, "per_gpu_batch": per_gpu_batch,
-                   "global_batch": per_gpu_batch * world, "parallelism": "dp%d" % world},
+    out.update({
         # algorithmic (direct-convolution, fp32-equivalent) flops of the launches this step actually made (conv + linear
         # kernels; the text encoder's library GEMMs, < 0.01 %, are not counted) over the step time.  NOT a fraction of any one
         # roof on the fp32 path (split-product launches run on the 16-bit
@@ -574,8 +622,6 @@ def measure(args, config_name, steps, warmup, dev, dist, rank, world, force_dp):
         "whole_step_tflops": round(step_tflops, 2),
         "algorithmic_gflop_per_image_executed": round(step_flops / per_gpu_batch / 1e9, 2),
         "algorithmic_gflop_per_image_survey": round(ALGO_GFLOP_PER_IMAGE_128 * (image_size / 128.0) ** 2, 2),
-        "loss_dis_all": round(float(trainer.loss_dis_all.detach()), 5),
-        "loss_gen_total": round(float(trainer.loss_gen_total.detach()), 5),
         "roofline": roof,
         "roofline_family_native": roof_family,
         "roofline_split_bf16x3": roof_x3,
@@ -583,16 +629,12 @@ def measure(args, config_name, steps, warmup, dev, dist, rank, world, force_dp):
         "decode_conv_stack": decode_stack,
         "kernel_spans": {k: {"launches": v["launches"], "ms": round(v["ms"], 3),
                              "tflops": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 2)} for k, v in spans.items()},
-    }
+    })
     if precision == "bf16":             # one pipe only: here the whole-step rate IS a fraction of a roof
         out["whole_step_frac_of_bf16_mfma_peak"] = round(step_tflops / (peak * world), 4)
     else:
         out["whole_step_fp32_equiv_tflops_vs_fp32_mfma_peak"] = round(step_tflops / (peak * world), 4)
-    if getattr(trainer, "_reducers", None):
-        out["data_parallel"] = {k: {"buckets": len(r.buckets), "bucket_mb": [round(b["flat"].numel() * 4 / 2 ** 20, 1) for b in r.buckets],
-                                    "all_reduces": r.calls, "launched_from_inside_backward": r.launched_early}
-                                for k, r in trainer._reducers.items()}
-    return out, (init_gen, init_dis)
+    return out, init_sd
 
 
 def main():
@@ -603,11 +645,18 @@ def main():
     ap.add_argument("--config", default="c1", choices=sorted(CONFIGS),
                     help="workload = BASELINE.json configs[i] (c1 fp32 128^2 B16, the default and headline; c2 bf16 128^2 B128; "
                          "c3 fp32 128^2 B64; c4 (alias c5) fp32 256^2 B8)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the instrumented last step (roofline, per-kernel table, decode "
+                         "conv stack), the default --also legs and, on one GPU, the CPU baseline.  A plain run (the default) sets "
+                         "up, warms up, times --steps steps, writes --dump-outputs and prints the record")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy: every loss (float64) and a "
+                         "fixed seeded sample of the updated G / D weights and their moving averages (float32), 32 MB in all")
     ap.add_argument("--also", default=None,
                     help="comma list of further workloads measured after the main one in the same process and reported under "
-                         "\"also\": {name: record} (default when the main workload is c1: c2 on one GPU, so that the bf16 "
-                         "configuration's images/s and roofline sit in every driver-timed record; c3,c4 -- BASELINE's own "
-                         "multi-GPU configurations -- on N > 1; 'none' switches it off)")
+                         "\"also\": {name: record} (default with --full when the main workload is c1: c2 on one GPU, so that the "
+                         "bf16 configuration's images/s and roofline sit in the full record; c3,c4 -- BASELINE's own multi-GPU "
+                         "configurations -- on N > 1; none without --full; 'none' switches it off)")
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"),
                     help="weak (default): fixed per-GPU batch; strong: fixed GLOBAL batch = the configuration's 8-GPU value "
                          "(c1 128, c2 1024, c3 512, c4 64; --global-batch overrides), split evenly over the ranks")
@@ -617,7 +666,7 @@ def main():
                          "shapes) and the per-kernel table to this JSON file (input of benchmarks/roofline_table.py)")
     ap.add_argument("--also-steps", type=int, default=10)
     ap.add_argument("--also-warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--cpu-warmup", type=int, default=3, help="CPU baseline: untimed iterations per thread count (BASELINE.md: >= 3)")
     ap.add_argument("--cpu-timed", type=int, default=5, help="CPU baseline: timed iterations per thread count (BASELINE.md: >= 5)")
     ap.add_argument("--cpu-threads", default="8,16,32,64",
@@ -669,11 +718,14 @@ def main():
             else:
                 dist.init_process_group("nccl", device_id=dev)      # "nccl" is RCCL on ROCm
 
-    out, init_sd = measure(args, args.config, args.steps, args.warmup, dev, dist, rank, world, force_dp)
+    # the kernel spans of the last timed step feed --full's figures and --ledger
+    instrument = args.full or bool(args.ledger)
+    out, init_sd = measure(args, args.config, args.steps, args.warmup, dev, dist, rank, world, force_dp,
+                           instrument=instrument, dump_dir=args.dump_outputs, keep_init=args.full)
 
     also = args.also
     if also is None:
-        plain = args.config == "c1" and not force_dp and args.per_gpu_batch is None
+        plain = args.full and args.config == "c1" and not force_dp and args.per_gpu_batch is None
         also = ("c2" if world == 1 else "c3,c4") if plain else "none"
     extra = {}
     for name in [n for n in also.split(",") if n and n != "none"]:
@@ -682,7 +734,7 @@ def main():
         import gc
         gc.collect()
         torch.cuda.empty_cache()
-        rec, _ = measure(args, name, args.also_steps, args.also_warmup, dev, dist, rank, world, force_dp)
+        rec, _ = measure(args, name, args.also_steps, args.also_warmup, dev, dist, rank, world, force_dp, instrument=instrument)
         if rec is not None:
             rec.pop("kernel_spans", None)
             extra[name] = rec
@@ -691,7 +743,7 @@ def main():
     if rank == 0:
         if extra:
             out["also"] = extra
-        if world == 1 and not args.no_cpu_baseline and not force_dp:
+        if args.full and world == 1 and not args.no_cpu_baseline and not force_dp:
             import contextlib
             import io
             from solver import Solver

@@ -214,6 +214,10 @@ def load():
         raise ImportError(
             "libdwcgan_hip.so not found at %s — build it with `make -C dwc-gan_amd/csrc` "
             "(or python -c 'import __graft_entry__ as g; g.build()'). There is no CPU fallback." % LIB_PATH)
+    # torch first: its bundled HIP runtime carries the soname the library links against (libamdhip64.so.7), so the library
+    # then binds to the runtime that owns torch's allocations and streams.  Loaded the other way round (build() followed by
+    # smoke() in one process), the system runtime is mapped beside torch's and every launch fails.
+    import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)     # AttributeError if the library does not export it
