@@ -191,6 +191,15 @@ SIGNATURES = {
     "dwc_bf16_blend_bwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
     "dwc_bf16_l1_mean_fwd": (c_int, [c_fp, c_fp, c_fp, c_sz, c_int, c_fp, c_sz, c_fp]),
     "dwc_bf16_l1_mean_bwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_sz, c_int, c_fp]),
+    "dwc_sn_layer_saved_floats": (c_sz, [c_int] * 3),
+    "dwc_sn_power_blocks": (c_int, [c_int, c_int, c_fp, c_fp]),
+    "dwc_sn_power_iteration": (c_int, [c_fp, c_int, c_int, c_int, c_fp, c_int, c_fp]),
+    "dwc_sn_epilogue_bwd_ws_bytes": (c_sz, [c_int] * 4),
+    "dwc_sn_epilogue_fwd": (c_int, [c_fp] * 4 + [c_int] * 4 + [c_fp, c_u, c_fp]),
+    "dwc_bf16_sn_epilogue_fwd": (c_int, [c_fp] * 4 + [c_int] * 4 + [c_fp]),
+    "dwc_sn_epilogue_bwd": (c_int, [c_fp] * 7 + [c_int] * 4 + [c_fp, c_sz, c_fp, c_u, c_fp]),
+    "dwc_bf16_sn_epilogue_bwd": (c_int, [c_fp] * 7 + [c_int] * 4 + [c_fp, c_sz, c_fp]),
+    "dwc_sn_weight_grad": (c_int, [c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_fp] + [c_int] * 4 + [c_fp]),
 }
 
 ABI_VERSION = 8                # DWC_ABI_VERSION of include/dwcgan_hip.h

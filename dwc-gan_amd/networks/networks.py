@@ -16,7 +16,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from hipdwc import ops
+from hipdwc import ops, spectral
 
 _CONV_ACTS = ("relu", "lrelu", "tanh", "sigmoid", "none")
 
@@ -74,6 +74,33 @@ class _PlainInstanceNorm(nn.InstanceNorm2d):
 # --------------------------------------------------------------------------------------
 # basic blocks
 # --------------------------------------------------------------------------------------
+class SpectralNorm(nn.Module):
+    """The reference's SpectralNorm(nn.Conv2d) wrapper (networks.py:754-816) as a parameter container: ``module`` is the convolution
+    with its ``weight`` replaced by ``weight_bar`` and the power-iteration vectors ``weight_u`` [Cout] / ``weight_v`` [Cin*kh*kw]
+    (Parameters without gradient: in the state_dict, not in the optimiser).  Construction draws like the reference's -- the
+    convolution's default init, then u ~ N(0, 1), then v ~ N(0, 1), both l2-normalised -- and ``weights_init`` passes it by (the
+    inner convolution has no ``weight``, the wrapper's class name does not start with Conv / Linear).  The iteration and the
+    normalised convolution run in Conv2dBlock.forward on hipdwc.spectral."""
+
+    def __init__(self, module, name="weight"):
+        super().__init__()
+        if name != "weight":
+            raise NotImplementedError("SpectralNorm of a parameter other than 'weight'")
+        self.module, self.name, self.power_iterations = module, name, 1
+        w = module.weight
+        height = w.data.shape[0]
+        width = w.view(height, -1).data.shape[1]
+        u = nn.Parameter(w.data.new(height).normal_(0, 1), requires_grad=False)
+        v = nn.Parameter(w.data.new(width).normal_(0, 1), requires_grad=False)
+        u.data = u.data / (u.data.norm() + 1e-12)
+        v.data = v.data / (v.data.norm() + 1e-12)
+        w_bar = nn.Parameter(w.data)
+        del module._parameters[name]
+        module.register_parameter(name + "_u", u)
+        module.register_parameter(name + "_v", v)
+        module.register_parameter(name + "_bar", w_bar)
+
+
 class Conv2dBlock(nn.Module):
     """pad -> conv -> norm -> activation (reference networks.py:524-585) as at most two fused passes.
 
@@ -82,7 +109,9 @@ class Conv2dBlock(nn.Module):
     add in the norm's apply pass.  The rest of the reference's signature is reachable too (r05), through stock PyTorch-ROCm DEVICE
     ops around the HIP convolution: ``pad_type`` zero / replicate at stride 1 (``F.pad``, then the convolution without padding), ``norm='bn'``
     (``nn.BatchNorm2d``), ``activation`` prelu / selu (``nn.PReLU`` / ``F.selu``), and any norm followed by an activation other than
-    ReLU (the norm unfused, then the activation).  ``norm='sn'`` (the reference's SpectralNorm wrapper) is not built."""
+    ReLU (the norm unfused, then the activation).  ``norm='sn'`` wraps the convolution in SpectralNorm like the reference: one power
+    iteration per call (``segments`` = S: the batch is S equal segments and segment s uses the s-th of S consecutive iterations), the
+    convolution on W_bar and 1 / sigma in a segmented epilogue (hipdwc.spectral)."""
 
     def __init__(self, input_dim, output_dim, kernel_size, stride, padding=0, norm="none", activation="relu",
                  pad_type="zero"):
@@ -110,13 +139,14 @@ class Conv2dBlock(nn.Module):
         elif norm == "none":
             self.norm = None
         elif norm == "sn":
-            raise NotImplementedError("norm='sn' (the reference's SpectralNorm wrapper, networks.py:755-800) is not built: no shipped "
-                                      "configuration uses it")
+            self.norm = None
         else:
             raise AssertionError("Unsupported normalization: {}".format(norm))
         if activation == "prelu":
             self.activation = nn.PReLU()
         self.conv = nn.Conv2d(input_dim, output_dim, kernel_size, stride, bias=self.use_bias)  # parameter container
+        if norm == "sn":
+            self.conv = SpectralNorm(self.conv)
 
     def _torch_act(self, y):
         if self.act_kind == "prelu":
@@ -125,9 +155,11 @@ class Conv2dBlock(nn.Module):
             return torch.nn.functional.selu(y)
         return {"lrelu": lambda t: torch.nn.functional.leaky_relu(t, 0.1), "tanh": torch.tanh, "sigmoid": torch.sigmoid}[self.act_kind](y)
 
-    def forward(self, x, residual=None, conv_token=None, res_token=None):
+    def forward(self, x, residual=None, conv_token=None, res_token=None, sn=None, segments=None):
         """``conv_token`` / ``res_token`` (hipdwc.ops.ResGradToken, both optional): this block's convolution opens / this block's
-        norm closes a residual block whose identity-branch gradient is added in the convolution's data-gradient epilogue."""
+        norm closes a residual block whose identity-branch gradient is added in the convolution's data-gradient epilogue.
+        norm='sn' only: ``sn`` = a hipdwc.spectral.SNRun that already holds this block's iterations (MsImageDis runs one for all its
+        SN layers), else ``segments`` (default 1) iterations are run here."""
         if x.shape[1] < 4:
             x = ops.pack_image(x)
         pad = self.padding
@@ -135,6 +167,13 @@ class Conv2dBlock(nn.Module):
             x = torch.nn.functional.pad(x, (pad,) * 4, mode="constant" if self.pad_type == "zero" else "replicate")
             pad = 0
         fused_act = self.act_kind in _CONV_ACTS
+        if self.norm_kind == "sn":
+            if sn is None:
+                sn = spectral.sn_power_iteration([self.conv.module], segments or 1)
+            y = spectral.sn_conv2d(x, self.conv.module, sn, self.stride, pad, self.act_kind if fused_act else "none", token=conv_token)
+            if not fused_act:
+                y = self._torch_act(y)
+            return y if residual is None else y + residual
         if self.norm is None:
             y = ops.conv2d(x, self.conv.weight, self.conv.bias, self.stride, pad, self.act_kind if fused_act else "none", token=conv_token)
             if not fused_act:
@@ -348,11 +387,27 @@ class MsImageDis(nn.Module):
         cls = nn.Conv2d(prev, self.num_cls, kernel_size=im_size // (2 ** self.n_layer), stride=1, padding=0, bias=False)
         return nn.Sequential(*chain), src, cls
 
-    def forward(self, x, use_multiscales=True):
+    def sn_layers(self, num_scales=None):
+        """The SpectralNorm containers of the first ``num_scales`` scales (all by default), in module order."""
+        n = self.num_scales if num_scales is None else num_scales
+        return [blk.conv.module for s in range(n) for blk in self.cnns_feat[s] if blk.norm_kind == "sn"]
+
+    def forward(self, x, use_multiscales=True, segments=None):
+        """``segments`` = S (dis.norm 'sn' only): x is S equal segments and segment s sees the weights of the s-th of S consecutive
+        reference calls -- each call of the reference runs one power iteration per SN layer (networks.py:775-785), so S calls on
+        the S segments equal this one pass.  None: one call, one iteration, as in the reference.  Without SN layers the segments
+        change nothing."""
         x = ops.pack_image(x)
         outputs = []
+        layers = self.sn_layers(self.num_scales if use_multiscales else 1)
+        sn = spectral.sn_power_iteration(layers, segments or 1) if layers else None
         for s in range(self.num_scales):
-            h = self.cnns_feat[s](x)
+            if sn is None:
+                h = self.cnns_feat[s](x)
+            else:
+                h = x
+                for blk in self.cnns_feat[s]:
+                    h = blk(h, sn=sn)
             src = ops.conv2d(h, self.cnns_src[s].weight, self.cnns_src[s].bias, 1, 0).float()   # losses are fp32 reductions
             cls = ops.conv2d(h, self.cnns_cls[s].weight, None, 1, 0).float()
             outputs.append([src, cls.reshape(cls.size(0), -1)])
@@ -367,13 +422,21 @@ class MsImageDis(nn.Module):
         two callers that differentiate it TWICE: Solver.gradient_penalty / r1_penalty (reference solver.py:291-315,338-350; off in the
         shipped configuration).  The HIP autograd Functions are once-differentiable; these penalties are an O(B) side branch of the D
         step, so they take torch's own double backward on the same parameters instead.  x: [B, 3, H, W] fp32."""
-        if self.norm != "none" or self.pad_type not in ("reflect", "zero", "replicate"):
+        if self.norm not in ("none", "sn") or self.pad_type not in ("reflect", "zero", "replicate"):
             raise NotImplementedError("gradient penalties: discriminator norm %r / pad %r" % (self.norm, self.pad_type))
         mode = {"reflect": "reflect", "zero": "constant", "replicate": "replicate"}[self.pad_type]
+        # norm 'sn': this call is one reference call on scale 0 -- one iteration of its SN layers (HIP), then W_bar / sigma in torch
+        layers = self.sn_layers(1)
+        if layers:
+            spectral.sn_power_iteration(layers, 1)
         h = x.float()
         for blk in self.cnns_feat[0]:
             p = blk.padding
-            h = F.conv2d(F.pad(h, (p, p, p, p), mode=mode) if p else h, blk.conv.weight, blk.conv.bias, stride=blk.stride)
+            if blk.norm_kind == "sn":
+                w, b = spectral.sn_weight_torch(blk.conv.module), blk.conv.module.bias
+            else:
+                w, b = blk.conv.weight, blk.conv.bias
+            h = F.conv2d(F.pad(h, (p, p, p, p), mode=mode) if p else h, w, b, stride=blk.stride)
             if blk.act_kind == "relu":
                 h = torch.relu(h)
             elif blk.act_kind == "lrelu":
@@ -408,8 +471,8 @@ class MsImageDis(nn.Module):
         return parts
 
     def adv_loss(self, outputs, B, labels, targets, w_src, w_cls):
-        """Adversarial objective of a BATCHED pass (segments of B samples: [x_fake | x_fake1 | x_real] in the D step,
-        [x_fake | x_fake1] in the G step), one tail launch per scale (hipdwc.ops.adv_tail) instead of the reference's term-by-term
+        """Adversarial objective of a BATCHED pass (segments of B samples: [x_fake | x_fake1 | x_real] in the D step --
+        [x_fake | x_real | x_fake1 | x_real] with spectral norm --, [x_fake | x_fake1] in the G step), one tail launch per scale (hipdwc.ops.adv_tail) instead of the reference's term-by-term
         LSGAN / BCE algebra (networks.py:116-170):  sum over scales and segments s of
         w_src[s] * mean((src_s - targets[s])^2) + w_cls[s] * BCEwithLogits(cls_s, labels).  LSGAN + CelebA/CUB200 only (the
         shipped configuration); anything else takes the term-by-term methods below."""

@@ -276,17 +276,23 @@ class Solver(nn.Module):
             # both fakes in ONE decoder pass (AdaIN parameters are per sample)
             fakes = self._decode(content, torch.cat([flat_heads(style_txt), style1]), torch.cat([x4, x4]), groups=2)
         gw, cw = configs["gan_w"], configs["cls_w"]
-        # ONE discriminator pass over [x_fake, x_fake1, x_real]; D(x_real) enters both loss terms as
-        # in the reference (which evaluates it twice, with identical values)
-        outs = self.dis(torch.cat([fakes, x4]))
+        if self.dis.sn_layers():
+            # spectral norm: each of the reference's four D calls x_fake, x_real, x_fake1, x_real (solver.py:333-336) runs one power
+            # iteration, so the two x_real passes see different weights -- ONE pass over the four segments, segment s at iteration s
+            outs = self.dis(torch.cat([fakes[:B], x4, fakes[B:], x4]), segments=4)
+            targets, w_src, w_cls, pairs = (0.0, 1.0, 0.0, 1.0), (gw,) * 4, (0.0, cw, 0.0, cw), ((0, 1), (2, 3))
+        else:
+            # ONE discriminator pass over [x_fake, x_fake1, x_real]; D(x_real) enters both loss terms as
+            # in the reference (which evaluates it twice, with identical values)
+            outs = self.dis(torch.cat([fakes, x4]))
+            targets, w_src, w_cls, pairs = (0.0, 0.0, 1.0), (gw, gw, 2.0 * gw), (0.0, 0.0, 2.0 * cw), ((0, 2), (1, 2))
         if self.dis.gan_type == "lsgan" and self.dis.dataset in ("CelebA", "CUB200"):
             # calc_dis_loss(x_fake, x_real) + calc_dis_loss(x_fake1, x_real) (reference solver.py:333-336), one tail launch per scale
-            self.loss_dis = self.dis.adv_loss(outs, B, label_src, targets=(0.0, 0.0, 1.0), w_src=(gw, gw, 2.0 * gw),
-                                              w_cls=(0.0, 0.0, 2.0 * cw))
+            self.loss_dis = self.dis.adv_loss(outs, B, label_src, targets=targets, w_src=w_src, w_cls=w_cls)
         else:
-            o_fake, o_fake1, o_real = self.dis.split_outputs(outs, [B, B, B])
-            self.loss_dis = self.dis.dis_loss_terms(o_fake, o_real, label_src, gw, cw) + \
-                self.dis.dis_loss_terms(o_fake1, o_real, label_src, gw, cw)
+            o = self.dis.split_outputs(outs, [B] * len(targets))
+            self.loss_dis = self.dis.dis_loss_terms(o[pairs[0][0]], o[pairs[0][1]], label_src, gw, cw) + \
+                self.dis.dis_loss_terms(o[pairs[1][0]], o[pairs[1][1]], label_src, gw, cw)
         self.loss_dis_all = self.loss_dis
         # Gradient / R1 penalties (reference solver.py:337-350; gp_w 0 and use_r1 False in the shipped configuration).  Both differentiate
         # the first scale's src map w.r.t. its INPUT and then that gradient w.r.t. D's weights: a double backward, taken on stock torch
@@ -356,7 +362,8 @@ class Solver(nn.Module):
             self.loss_gen_recon_s_rand = self.criterion_l1(style_rand, style1)
             self.loss_gen_cycrecon_x = ops.l1_mean(x_cycle, x4, image=True) if cyc else 0
 
-            outs = self.dis(x_all[B:])                                          # one pass over [x_fake, x_fake1]
+            # one pass over [x_fake, x_fake1] (spectral norm: the reference's two calls, one iteration each)
+            outs = self.dis(x_all[B:], segments=2 if self.dis.sn_layers() else None)
             if self.dis.gan_type == "lsgan" and self.dis.dataset in ("CelebA", "CUB200"):
                 self.loss_gen_adv = self.dis.adv_loss(outs, B, label_trg, targets=(1.0, 1.0), w_src=(cfg["gan_w"],) * 2,
                                                       w_cls=(cfg["cls_w"],) * 2)

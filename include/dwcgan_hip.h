@@ -652,6 +652,43 @@ int dwc_bf16_blend_bwd(const void* dout, const void* heads, const void* real, vo
 int dwc_bf16_l1_mean_fwd(const void* a, const void* b, float* out, size_t n, int skip4, void* ws, size_t ws_bytes, void* stream);
 int dwc_bf16_l1_mean_bwd(const void* a, const void* b, const float* dout, void* da, void* db, size_t n, int skip4, void* stream);
 
+/* ---- spectral normalisation, Conv2dBlock(norm='sn') (spectral_norm.hip; reference networks.py:754-816) ----------------------
+ * W_bar [Cout][K] (K = Cin*KH*KW), eps = 1e-12.  Iteration s: t = W_bar^T u_{s-1}, v_s = t / (|t| + eps), w = W_bar v_s,
+ * u_s = w / (|w| + eps), r_s = 1 / (u_s . w); u_{-1} = the layer's weight_u as stored.
+ * dwc_sn_power_iteration runs S iterations for L layers in 2 S + 1 launches, no host synchronisation, fixed-order reductions
+ * (bit-identical results run to run).  Per layer the caller's fp32 buffer `base` holds, at the descriptor's float offsets,
+ * U [S][Cout] (u_s rows), V [S][K] (v_s rows) and R [S] (r_s): dwc_sn_layer_saved_floats(S, Cout, K) floats per layer (each
+ * part rounded up to 4 floats).  The last u / v are written into the parameters.  A layer's column blocks start at col_blk0
+ * (dwc_sn_power_blocks: ceil(K / 64) of them), its row blocks at row_blk0 (ceil(Cout / 8)); col_blocks / row_blocks are the
+ * totals.  vec != 0: K % 4 == 0 and W_bar 16-byte aligned.  Cout <= 1024, K <= 8192. */
+typedef struct {
+    const float* w;                  /* W_bar, fp32 [Cout][K] */
+    float* u;                        /* weight_u [Cout]: read at s = 0, written at the end */
+    float* v;                        /* weight_v [K]: written at the end */
+    long long off_u, off_v, off_r;   /* float offsets of U / V / R in `base` */
+    int cout, k, col_blk0, row_blk0, vec, reserved;
+} dwc_sn_desc;
+size_t dwc_sn_layer_saved_floats(int S, int cout, int k);
+int dwc_sn_power_blocks(int cout, int k, int* col_blocks, int* row_blocks);
+int dwc_sn_power_iteration(const dwc_sn_desc* desc_dev, int L, int col_blocks, int row_blocks, float* base, int S, void* stream);
+/* Segmented epilogue of a convolution run on W_bar (no bias, no activation): Z [rows][C] NHWC (C a multiple of 4 fp32 / 8 bf16),
+ * rows = S equal segments;  y = act(Z * r[s] + b), act in {none, relu, lrelu, tanh, sigmoid}; b [C] fp32 (zero padded).
+ * _bwd, one pass over dy and Z: g = dy * act'(.), dZ = g * r[s], db[C] = sum g (db may be NULL), c[s] = <g_s, Z_s>; fixed-order
+ * partials in ws (dwc_sn_epilogue_bwd_ws_bytes(rows, C, S, 4 fp32 / 8 bf16)), no atomics; C / vec <= 256.  The fp32 forms raise
+ * the absmax slot of y / dZ (NULL: none). */
+size_t dwc_sn_epilogue_bwd_ws_bytes(int rows, int C, int S, int vec);
+int dwc_sn_epilogue_fwd(const float* Z, const float* r, const float* b, float* y, int rows, int C, int S, int act, void* y_amax,
+                        unsigned y_epoch, void* stream);
+int dwc_bf16_sn_epilogue_fwd(const void* Z, const float* r, const float* b, void* y, int rows, int C, int S, int act, void* stream);
+int dwc_sn_epilogue_bwd(const float* dy, const float* Z, const float* r, const float* b, float* dZ, float* db, float* c, int rows, int C,
+                        int S, int act, void* ws, size_t ws_bytes, void* dz_amax, unsigned dz_epoch, void* stream);
+int dwc_bf16_sn_epilogue_bwd(const void* dy, const void* Z, const float* r, const float* b, void* dZ, float* db, float* c, int rows,
+                             int C, int S, int act, void* ws, size_t ws_bytes, void* stream);
+/* Gradient through sigma (u, v held constant): dw[Cout][K] = (accumulate ? dw : 0) - sum_s c[s] r[s]^2 u_s v_s^T with
+ * u_s = U + s * u_stride, v_s = V + s * v_stride (stride 0: the same pair for every s). */
+int dwc_sn_weight_grad(const float* U, int u_stride, const float* V, int v_stride, const float* r, const float* c, float* dw, int S,
+                       int cout, int k, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
