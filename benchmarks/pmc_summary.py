@@ -55,11 +55,11 @@ def main():
     fetch, write = per_kernel(fetch_dir, "FETCH_SIZE"), per_kernel(write_dir, "WRITE_SIZE")
     keep = ("conv_gemm_kernel", "wino_fused_kernel", "conv_gemm_batched_kernel", "conv_gemm_strips_kernel", "wino_input_kernel", "wino_output_kernel",
             "wino_dy_kernel", "wino_wgrad_reduce_kernel", "conv_wgrad_kernel", "wgrad_reduce_kernel", "in_stats_partial",
-            "gemm_kernel_h", "conv_halo_kernel", "gemm_strips_kernel_h", "wgrad_kernel_h", "wgrad_reduce_kernel_h", "fold_ring_kernel_h",
-            "fold_reflect_kernel_h", "splitk_reduce_kernel_h", "in_bwd_partial", "upsample2x_bwd_kernel", "ln_bwd_apply",
+            "gemm_kernel_h", "conv_halo_kernel", "gemm_strips_kernel_h", "wgrad_kernel_h", "splitk_reduce_kernel",
+            "in_bwd_partial", "upsample2x_bwd_kernel", "ln_bwd_apply",
             "in_apply", "in_bwd_apply", "act_bwd_partial", "fold_reflect_kernel", "fold_ring_kernel", "upsample2x_fwd_kernel",
             "ln_apply", "adam_multi_kernel", "ema_multi_kernel", "lstm_step_fwd", "lstm_step_bwd",
-            "conv_halo_x3_kernel", "wgrad_x3_kernel", "x3_wgrad_reduce_kernel", "wgrad_halo_kernel", "wgrad_halo_reduce_kernel",
+            "conv_halo_x3_kernel", "wgrad_x3_kernel", "x3_wgrad_reduce_kernel", "wgrad_halo_kernel",
             "conv_narrow_kernel", "conv_stem_kernel", "smallk_wgrad_kernel", "smallk_reduce_kernel",
             "conv_halo16_kernel", "fold_reflect_kernel_h8", "lstm_seq_fwd", "lstm_seq_bwd", "weight_refresh_multi_kernel",
             "adv_tail_fwd_kernel", "adv_tail_bwd_kernel", "maxpool2_fwd_kernel", "in_stats_final", "ln_bwd_partial")
@@ -75,6 +75,7 @@ def main():
         res["kernels"][k] = {"FETCH_SIZE_KiB_avg_per_launch": round(f_avg, 1), "launches": fetch[k][1],
                              "WRITE_SIZE_KiB_avg_per_launch": round(w_avg, 1),
                              "hbm_bytes_per_launch_corrected": int((2 * f_avg + w_avg) * 1024)}
+    # (the fold / reduce / weight-layout kernels of csrc/conv_fold.h are templates on the element type: one name for fp32 and bf16)
     # per instantiation family ("name<first template argument>"): what bench.py's single-kernel `roofline.traffic` reads
     fetch_k, write_k = per_kernel(fetch_dir, "FETCH_SIZE", True), per_kernel(write_dir, "WRITE_SIZE", True)
     res["kernels_k"] = {}
@@ -90,7 +91,7 @@ def main():
               "wino_input_kernel", "wino_output_kernel", "fold_ring_kernel",
               # bf16 path (bench --config c2): im2col GEMM, halo-tiled kernel, ring strips + folds, split-K reduce
               "gemm_kernel_h", "conv_halo_kernel", "conv_halo16_kernel", "conv_narrow_kernel", "conv_stem_kernel", "gemm_strips_kernel_h",
-              "fold_ring_kernel_h", "fold_reflect_kernel_h", "fold_reflect_kernel_h8", "splitk_reduce_kernel_h")
+              "fold_reflect_kernel", "fold_reflect_kernel_h8", "splitk_reduce_kernel")
     steps = int(sys.argv[4]) if len(sys.argv) > 4 else 3
     spans_per_step = int(sys.argv[5]) if len(sys.argv) > 5 else 236
     res["config"] = sys.argv[6] if len(sys.argv) > 6 else "c1"

@@ -17,7 +17,7 @@
 // ds_read_b64_tr_b16 (a 4-pixel x 16-channel block per 16 lanes, delivered channel-major).
 #include <type_traits>
 
-#include "conv_geom.h"
+#include "conv_fold.h"
 
 namespace {
 
@@ -398,22 +398,6 @@ __global__ __launch_bounds__(256) void gemm_strips_kernel_h(StripSet ss) {
                                                 blockIdx.x, s.tiles);
 }
 
-// dst[i] = act(sum_s part[s][i] + bias[i % N]) rounded to bf16, fixed summation order
-__global__ __launch_bounds__(256) void splitk_reduce_kernel_h(const float* __restrict__ part, bf16* __restrict__ dst,
-                                                              const float* __restrict__ bias, size_t total4, size_t stride4,
-                                                              int splits, int N, int act) {
-    const int nq = N >> 2;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) {
-        f32x4 s = reinterpret_cast<const f32x4*>(part)[i];
-        for (int z = 1; z < splits; ++z) s += reinterpret_cast<const f32x4*>(part)[(size_t)z * stride4 + i];
-        const int c4 = i % nq;
-        if (bias) s += reinterpret_cast<const f32x4*>(bias)[c4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s[k] = dwc_act_apply(s[k], act, c4 * 4 + k);
-        reinterpret_cast<bf16x4*>(dst)[i] = pack4(s[0], s[1], s[2], s[3]);
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // weight gradient: dW[k][n] = sum_m A[m][k] * dY[m][n], tile 128(k) x BN(n), pixels in slabs of 64, split over pixel
 // ranges into fp32 slabs.  LDS tiles are row-major [pixel][channel]; 16-byte chunk c of pixel row m is stored at chunk
@@ -630,52 +614,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel_h(Gather g, const bf16* __re
 #endif
 }
 
-// slab[s][(kh,kw,ci)][co] summed over s -> dw[co][ci][kh][kw] (state_dict layout, fp32), real channels only
-__global__ void wgrad_reduce_kernel_h(const float* __restrict__ slab, float* __restrict__ dw, int splits, int K, int N, int Cin,
-                                      int KHW, int cin_real, int cout_real) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)K * N) return;
-    const int co = idx % N;
-    const int k = idx / N;
-    const int ci = k % Cin, tap = k / Cin;
-    if (co >= cout_real || ci >= cin_real) return;
-    float s = 0.f;
-    for (int z = 0; z < splits; ++z) s += slab[(size_t)z * K * N + idx];
-    dw[((size_t)co * cin_real + ci) * KHW + tap] = s;
-}
-
-// reflect-pad adjoint on bf16 images (fp32 accumulation)
-__global__ void fold_reflect_kernel_h(const bf16* __restrict__ gp, bf16* __restrict__ dx, int B, int H, int W, int C4, int pad,
-                                      int Wp) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t total = (size_t)B * H * W * C4;
-    if (idx >= total) return;
-    const int c = idx % C4;
-    size_t r = idx / C4;
-    const int w = r % W;
-    r /= W;
-    const int h = r % H;
-    const int n = r / H;
-    const int Hp = H + 2 * pad;
-    int hs[3], ws[3], nh = 0, nw = 0;
-    hs[nh++] = h + pad;
-    if (h >= 1 && h <= pad) hs[nh++] = pad - h;
-    if (h >= H - 1 - pad && h <= H - 2) hs[nh++] = pad + 2 * (H - 1) - h;
-    ws[nw++] = w + pad;
-    if (w >= 1 && w <= pad) ws[nw++] = pad - w;
-    if (w >= W - 1 - pad && w <= W - 2) ws[nw++] = pad + 2 * (W - 1) - w;
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    const bf16x4* g4 = reinterpret_cast<const bf16x4*>(gp);
-    for (int a = 0; a < nh; ++a)
-        for (int b = 0; b < nw; ++b) {
-            const bf16x4 v = g4[((size_t)(n * Hp + hs[a]) * Wp + ws[b]) * C4 + c];
-            s += f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-        }
-    reinterpret_cast<bf16x4*>(dx)[idx] = pack4(s[0], s[1], s[2], s[3]);
-}
-
-// the same with 16-byte accesses (8 channels per lane) and a (W*C8 / 256, H, B) grid: no per-element 64-bit divisions.  r02: the
-// 8-byte form ran at 3.5 TB/s on the stride-2 data gradients of configs[2] (3.4 ms per step).
+// fold_reflect_kernel (conv_fold.h) with 16-byte accesses (8 channels per lane) and a (W*C8 / 256, H, B) grid: no per-element 64-bit
+// divisions.  r02: the 8-byte form ran at 3.5 TB/s on the stride-2 data gradients of configs[2] (3.4 ms per step).
 __global__ __launch_bounds__(256) void fold_reflect_kernel_h8(const bf16* __restrict__ gp, bf16* __restrict__ dx, int H, int W, int C8,
                                                               int pad, int Wp) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -684,167 +624,18 @@ __global__ __launch_bounds__(256) void fold_reflect_kernel_h8(const bf16* __rest
     const int h = blockIdx.y;
     const size_t n = blockIdx.z;
     const int Hp = H + 2 * pad;
-    int hs[3], ws[3], nh = 0, nw = 0;
-    hs[nh++] = h + pad;
-    if (h >= 1 && h <= pad) hs[nh++] = pad - h;
-    if (h >= H - 1 - pad && h <= H - 2) hs[nh++] = pad + 2 * (H - 1) - h;
-    ws[nw++] = w + pad;
-    if (w >= 1 && w <= pad) ws[nw++] = pad - w;
-    if (w >= W - 1 - pad && w <= W - 2) ws[nw++] = pad + 2 * (W - 1) - w;
-    float s[8];
+    int hs[3], ws[3];
+    const int nh = reflect_src(h, H, pad, hs), nw = reflect_src(w, W, pad, ws);
+    float s[8], v[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) s[k] = 0.f;
-    const bf16x8* g8 = reinterpret_cast<const bf16x8*>(gp);
     for (int a = 0; a < nh; ++a)
         for (int b = 0; b < nw; ++b) {
-            const bf16x8 v = g8[((n * Hp + hs[a]) * (size_t)Wp + ws[b]) * C8 + c];
+            ldv(gp, ((n * Hp + hs[a]) * (size_t)Wp + ws[b]) * C8 + c, v);
 #pragma unroll
-            for (int k = 0; k < 8; ++k) s[k] += (float)v[k];
+            for (int k = 0; k < 8; ++k) s[k] += v[k];
         }
-    bf16x8 o;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) o[k] = (bf16)s[k];
-    reinterpret_cast<bf16x8*>(dx)[((n * H + h) * (size_t)W + w) * C8 + c] = o;
-}
-
-// dx (holds the interior of the padded gradient image already: Scatter::crop) += the border ring of gp folded back by the reflect
-// rule.  Only the pixels a ring pixel folds onto are touched: rows 1..pad and H-1-pad..H-2 (whole rows), and columns 1..pad and
-// W-1-pad..W-2 of the other rows.
-__global__ __launch_bounds__(256) void fold_band_kernel_h8(const bf16* __restrict__ gp, bf16* __restrict__ dx, int B, int H, int W, int C8,
-                                                                    int pad, int Wp) {
-    // one thread per (image, band pixel, channel chunk): per image the 2*pad band rows whole (W pixels each), then the 2*pad band
-    // columns of the H - 2*pad other rows
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const int rows_done = 2 * pad, rest = H - 2 * pad;          // band rows, other rows
-    const int band = rows_done * W + rest * 2 * pad;            // band pixels per image
-    const size_t total = (size_t)B * band * C8;
-    if (idx >= total) return;
-    const int c = idx % C8;
-    size_t r = idx / C8;
-    const int q = r % band;
-    const size_t n = r / band;
-    const int Hp = H + 2 * pad;
-    int h, w;
-    if (q < rows_done * W) {
-        const int br = q / W;
-        w = q - br * W;
-        h = br < pad ? 1 + br : H - 1 - pad + (br - pad);
-    } else {
-        const int q2 = q - rows_done * W;
-        const int hr = q2 / (2 * pad), k = q2 - hr * 2 * pad;
-        // the hr-th row that is NOT a band row: rows 0, pad+1 .. H-2-pad, H-1
-        h = hr == 0 ? 0 : (hr == rest - 1 ? H - 1 : pad + hr);
-        w = k < pad ? 1 + k : W - 1 - pad + (k - pad);
-    }
-    int hs[3], ws[3], nh = 0, nw = 0;
-    hs[nh++] = h + pad;
-    if (h >= 1 && h <= pad) hs[nh++] = pad - h;
-    if (h >= H - 1 - pad && h <= H - 2) hs[nh++] = pad + 2 * (H - 1) - h;
-    ws[nw++] = w + pad;
-    if (w >= 1 && w <= pad) ws[nw++] = pad - w;
-    if (w >= W - 1 - pad && w <= W - 2) ws[nw++] = pad + 2 * (W - 1) - w;
-    if (nh * nw == 1) return;
-    const size_t o = ((n * H + h) * (size_t)W + w) * C8 + c;
-    const bf16x8 cur = reinterpret_cast<const bf16x8*>(dx)[o];
-    float s[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s[k] = (float)cur[k];
-    const bf16x8* g8 = reinterpret_cast<const bf16x8*>(gp);
-    for (int a = 0; a < nh; ++a)
-        for (int b = 0; b < nw; ++b) {
-            if (a == 0 && b == 0) continue;               // the pixel's own (interior) value is in dx already
-            const bf16x8 v = g8[((n * Hp + hs[a]) * (size_t)Wp + ws[b]) * C8 + c];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s[k] += (float)v[k];
-        }
-    bf16x8 res;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) res[k] = (bf16)s[k];
-    reinterpret_cast<bf16x8*>(dx)[o] = res;
-}
-
-// dx (bf16, holds the interior) += the fp32 border ring folded back by the reflect rule (see fold_ring_kernel, conv_igemm.hip)
-__global__ void fold_ring_kernel_h(bf16* __restrict__ dx, const float* __restrict__ ring, size_t off_bottom, size_t off_left,
-                                   size_t off_right, int parts, size_t part_stride, int B, int H, int W, int C4, int pad) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int band = 2 * pad * (W + H);
-    const size_t total = (size_t)B * band * C4;
-    if (idx >= total) return;
-    const int c = idx % C4;
-    size_t r = idx / C4;
-    const int q = r % band;
-    const int n = r / band;
-    int h, w;
-    if (q < 2 * pad * W) {
-        const int br = q / W;
-        w = q - br * W;
-        h = br < pad ? 1 + br : H - 1 - pad + (br - pad);
-    } else {
-        const int q2 = q - 2 * pad * W, bc = q2 / H;
-        h = q2 - bc * H;
-        w = bc < pad ? 1 + bc : W - 1 - pad + (bc - pad);
-        if ((h >= 1 && h <= pad) || (h >= H - 1 - pad && h <= H - 2)) return;
-    }
-    if (h < 0 || h >= H || w < 0 || w >= W) return;
-    const int Wp = W + 2 * pad;
-    int hs[3], ws[3], nh = 0, nw = 0;
-    hs[nh++] = h + pad;
-    if (h >= 1 && h <= pad) hs[nh++] = pad - h;
-    if (h >= H - 1 - pad && h <= H - 2) hs[nh++] = pad + 2 * (H - 1) - h;
-    ws[nw++] = w + pad;
-    if (w >= 1 && w <= pad) ws[nw++] = pad - w;
-    if (w >= W - 1 - pad && w <= W - 2) ws[nw++] = pad + 2 * (W - 1) - w;
-    bf16x4* out = reinterpret_cast<bf16x4*>(dx) + ((size_t)(n * H + h) * W + w) * C4 + c;
-    const bf16x4 cur = *out;
-    f32x4 s = {(float)cur[0], (float)cur[1], (float)cur[2], (float)cur[3]};
-    for (int a = 0; a < nh; ++a)
-        for (int b = 0; b < nw; ++b) {
-            if (a == 0 && b == 0) continue;
-            const int rh = hs[a], rw = ws[b];
-            size_t e;
-            if (rh < pad) e = ((size_t)(n * pad + rh) * Wp + rw) * C4;
-            else if (rh >= pad + H) e = off_bottom / 4 + ((size_t)(n * pad + rh - pad - H) * Wp + rw) * C4;
-            else if (rw < pad) e = off_left / 4 + ((size_t)(n * H + rh - pad) * pad + rw) * C4;
-            else e = off_right / 4 + ((size_t)(n * H + rh - pad) * pad + rw - pad - W) * C4;
-            for (int p = 0; p < parts; ++p) s += reinterpret_cast<const f32x4*>(ring + p * part_stride)[e + c];
-        }
-    *out = pack4(s[0], s[1], s[2], s[3]);
-}
-
-// fp32 OIHW master weights -> bf16 [N][Kp] streaming layouts (see conv_igemm.hip: same orderings, Kp a multiple of 64)
-__global__ void weight_prepare_fwd_kernel_h(const float* __restrict__ w, bf16* __restrict__ out, int Cout, int Cin, int KHW,
-                                            int cout_pad, int cin_pad, int Kp) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)cout_pad * Kp) return;
-    const int k = idx % Kp, co = idx / Kp;
-    const int ci = k % cin_pad, tap = k / cin_pad;
-    float v = 0.f;
-    if (co < Cout && ci < Cin && tap < KHW) v = w[((size_t)co * Cin + ci) * KHW + tap];
-    out[idx] = (bf16)v;
-}
-
-__global__ void weight_prepare_dgrad_kernel_h(const float* __restrict__ w, bf16* __restrict__ out, int Cout, int Cin, int KH, int KW,
-                                              int stride, int cout_pad, int cin_pad, int Kp) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t per_class = (size_t)cin_pad * Kp;
-    const int classes = stride == 1 ? 1 : 4;
-    if (idx >= per_class * classes) return;
-    const int cls = idx / per_class;
-    const size_t r = idx % per_class;
-    const int k = r % Kp, ci = r / Kp;
-    const int co = k % cout_pad, tapo = k / cout_pad;
-    int kh, kw;
-    bool ok = co < Cout && ci < Cin;
-    if (stride == 1) {
-        ok = ok && tapo < KH * KW;
-        kh = KH - 1 - tapo / KW;
-        kw = KW - 1 - tapo % KW;
-    } else {
-        ok = ok && tapo < 4;
-        kh = (cls >> 1) + 2 * (tapo >> 1);
-        kw = (cls & 1) + 2 * (tapo & 1);
-    }
-    out[idx] = (bf16)(ok ? w[((size_t)co * Cin + ci) * KH * KW + kh * KW + kw] : 0.f);
+    stv(dx, ((n * H + h) * (size_t)W + w) * C8 + c, s);
 }
 
 // ---- launchers -------------------------------------------------------------------------------
@@ -926,14 +717,17 @@ int launch_gemm_h(const Gather& g, const bf16* w, size_t w_class_stride, int cla
     else if (p.bm == 64 && p.bn == 64) launch_variant_h<64, 64, 2, 2, 1, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
     else launch_variant_h<128, 32, 4, 1, 1, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
     DWC_LAUNCH_CHECK();
-    if (p.splits > 1) {
-        const size_t total4 = dst_elems / 4;
-        size_t blocks = (total4 + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel_h, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)ws, final_dst, bias, total4,
-                           total4, p.splits, o.N, act);
-        DWC_LAUNCH_CHECK();
-    }
+    if (p.splits > 1) return splitk_reduce((const float*)ws, final_dst, bias, dst_elems, p.splits, o.N, act, st);
+    return DWC_OK;
+}
+
+// The ring strips of a data gradient (same_dgrad_geom / s2_ring_geom built with row tiles of bm = strip_bm(..., half = true)).
+// F32OUT: fp32 partial strips for fold_ring; otherwise whole-K strips rounded to bf16 at their place in the padded image.
+template <bool F32OUT>
+int launch_strips(const StripSet& ss, int bm, dim3 grid, hipStream_t st) {
+    if (bm == 128) hipLaunchKernelGGL((gemm_strips_kernel_h<128, 64, 2, 2, 2, 1, F32OUT>), grid, dim3(256), 0, st, ss);
+    else hipLaunchKernelGGL((gemm_strips_kernel_h<64, 64, 2, 2, 1, 1, F32OUT>), grid, dim3(256), 0, st, ss);
+    DWC_LAUNCH_CHECK();
     return DWC_OK;
 }
 
@@ -963,10 +757,7 @@ int wgrad_launch_h(const FwdGeom& f, const bf16* dy, float* dw_oihw, int Cin, in
         hipLaunchKernelGGL((wgrad_kernel_h<32, 4, 1, 1, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
     }
     DWC_LAUNCH_CHECK();
-    const size_t total = (size_t)g.K * Cout;
-    if (!wgrad_reduce_wide(slab, dw_oihw, splits, g.K, Cout, Cin, KHW, cin_real, cout_real, st))
-        hipLaunchKernelGGL(wgrad_reduce_kernel_h, dim3((total + 255) / 256), dim3(256), 0, st, slab, dw_oihw, splits, g.K, Cout, Cin, KHW,
-                           cin_real, cout_real);
+    wgrad_reduce(slab, dw_oihw, splits, g.K, Cout, Cin, KHW, cin_real, cout_real, st);
     DWC_LAUNCH_CHECK();
     return DWC_OK;
 }
@@ -976,20 +767,13 @@ int wgrad_launch_h(const FwdGeom& f, const bf16* dy, float* dw_oihw, int Cin, in
 extern "C" {
 
 size_t dwc_bf16_weight_prepared_elems(int Cout, int Cin, int KH, int KW, int stride, int cout_pad, int cin_pad, int for_dgrad) {
-    if (!for_dgrad) return (size_t)cout_pad * ((KH * KW * cin_pad + BK - 1) / BK * BK);
-    if (stride == 1) return (size_t)cin_pad * ((KH * KW * cout_pad + BK - 1) / BK * BK);
-    return (size_t)4 * cin_pad * ((4 * cout_pad + BK - 1) / BK * BK);
+    return weight_prepared_elems(KH, KW, stride, cout_pad, cin_pad, for_dgrad, BK);
 }
 
 int dwc_bf16_weight_prepare_fwd(const float* w, void* out, int Cout, int Cin, int KH, int KW, int cout_pad, int cin_pad,
                                 void* stream) {
     if (cout_pad < Cout || cin_pad < Cin) return DWC_EINVAL;
-    const int Kp = (KH * KW * cin_pad + BK - 1) / BK * BK;
-    const size_t total = (size_t)cout_pad * Kp;
-    hipLaunchKernelGGL(weight_prepare_fwd_kernel_h, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (bf16*)out, Cout,
-                       Cin, KH * KW, cout_pad, cin_pad, Kp);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    return weight_prepare_fwd(w, (bf16*)out, Cout, Cin, KH, KW, cout_pad, cin_pad, BK, (hipStream_t)stream);
 }
 
 int dwc_bf16_weight_prepare_dgrad(const float* w, void* out, int Cout, int Cin, int KH, int KW, int stride, int cout_pad,
@@ -997,12 +781,7 @@ int dwc_bf16_weight_prepare_dgrad(const float* w, void* out, int Cout, int Cin, 
     if (cout_pad < Cout || cin_pad < Cin) return DWC_EINVAL;
     if (stride == 2 && !(KH == 4 && KW == 4)) return DWC_EINVAL;
     if (stride != 1 && stride != 2) return DWC_EINVAL;
-    const int Kp = ((stride == 1 ? KH * KW : 4) * cout_pad + BK - 1) / BK * BK;
-    const size_t total = (size_t)(stride == 1 ? 1 : 4) * cin_pad * Kp;
-    hipLaunchKernelGGL(weight_prepare_dgrad_kernel_h, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (bf16*)out,
-                       Cout, Cin, KH, KW, stride, cout_pad, cin_pad, Kp);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    return weight_prepare_dgrad(w, (bf16*)out, Cout, Cin, KH, KW, stride, cout_pad, cin_pad, BK, (hipStream_t)stream);
 }
 
 size_t dwc_bf16_conv2d_fwd_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
@@ -1082,12 +861,7 @@ int dwc_bf16_conv2d_bwd_data_fold(const void* dy, const void* w_dgrad, void* dxp
     int rc = launch_gemm_h(f.g, (const bf16*)w_dgrad, f.wcs, f.classes, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, ws, ws_bytes, st);
     if (rc != DWC_OK) return rc;
     if (!direct) return dwc_bf16_reflect_pad_adjoint(dxp, dx, B, H, W, Cin, pad, stream);
-    const int C8 = Cin / 8;
-    const size_t band_items = (size_t)B * (2 * pad * W + (H - 2 * pad) * 2 * pad) * C8;
-    hipLaunchKernelGGL(fold_band_kernel_h8, dim3((unsigned)((band_items + 255) / 256)), dim3(256), 0, st, (const bf16*)dxp, (bf16*)dx, B, H, W,
-                       C8, pad, W + 2 * pad);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    return fold_band((const bf16*)dxp, (bf16*)dx, B, H, W, Cin, pad, st);
 }
 
 /* bf16 twin of dwc_conv2d_bwd_data_s2_ring: ring of the padded gradient image of a 4x4 stride-2 reflect-pad-1 convolution as eight
@@ -1100,28 +874,16 @@ int dwc_bf16_conv2d_bwd_data_s2_ring(const void* dy, const void* w_dgrad, void* 
         !s2_ring_geom(dy, w_dgrad, dxp, 2, B, H, W, Cin, Cout, &f, BK, MIN_LOG_C, bm))
         return DWC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (bm == 128) hipLaunchKernelGGL((gemm_strips_kernel_h<128, 64, 2, 2, 2, 1, false>), dim3(f.max_tiles, 1, 8), dim3(256), 0, st, f.ss);
-    else hipLaunchKernelGGL((gemm_strips_kernel_h<64, 64, 2, 2, 1, 1, false>), dim3(f.max_tiles, 1, 8), dim3(256), 0, st, f.ss);
-    DWC_LAUNCH_CHECK();
-    const int C8 = Cin / 8;
-    const size_t band_items = (size_t)B * (2 * W + (H - 2) * 2) * C8;
-    hipLaunchKernelGGL(fold_band_kernel_h8, dim3((unsigned)((band_items + 255) / 256)), dim3(256), 0, st, (const bf16*)dxp, (bf16*)dx, B, H, W,
-                       C8, 1, W + 2);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    const int rc = launch_strips<false>(f.ss, bm, dim3(f.max_tiles, 1, 8), st);
+    if (rc != DWC_OK) return rc;
+    return fold_band((const bf16*)dxp, (bf16*)dx, B, H, W, Cin, 1, st);
 }
 
 /* dx (already holding the interior of the padded gradient image dxp) += the border ring of dxp folded back by the reflect rule:
  * the second half of dwc_bf16_conv2d_bwd_data_fold for producers with their own epilogue (dwc_bf16_conv2d_stem_crop). */
 int dwc_bf16_reflect_pad_adjoint_band(const void* dxp, void* dx, int B, int H, int W, int C, int pad, void* stream) {
     if (B <= 0 || (C & 7) || pad <= 0 || H < 2 * pad + 2 || W < 2 * pad + 2 || H > 65535 || B > 65535) return DWC_EINVAL;
-    const int C8 = C / 8;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t band_items = (size_t)B * (2 * pad * W + (H - 2 * pad) * 2 * pad) * C8;
-    hipLaunchKernelGGL(fold_band_kernel_h8, dim3((unsigned)((band_items + 255) / 256)), dim3(256), 0, st, (const bf16*)dxp, (bf16*)dx, B, H, W,
-                       C8, pad, W + 2 * pad);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    return fold_band((const bf16*)dxp, (bf16*)dx, B, H, W, C, pad, (hipStream_t)stream);
 }
 
 int dwc_bf16_reflect_pad_adjoint(const void* dxp, void* dx, int B, int H, int W, int C, int pad, void* stream) {
@@ -1132,11 +894,7 @@ int dwc_bf16_reflect_pad_adjoint(const void* dxp, void* dx, int B, int H, int W,
         DWC_LAUNCH_CHECK();
         return DWC_OK;
     }
-    const size_t total = (size_t)B * H * W * (C / 4);
-    hipLaunchKernelGGL(fold_reflect_kernel_h, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const bf16*)dxp,
-                       (bf16*)dx, B, H, W, C / 4, pad, W + 2 * pad);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    return fold_reflect((const bf16*)dxp, (bf16*)dx, B, H, W, C / 4, pad, W + 2 * pad, (hipStream_t)stream);
 }
 
 size_t dwc_bf16_conv2d_bwd_data_same_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int pad) {
@@ -1160,15 +918,9 @@ static int same_dgrad_run_h(const void* dy, const void* w_dgrad, const void* w_d
                                ws_bytes - ring_bytes, st);
         if (rc != DWC_OK) return rc;
     }
-    if (bm == 128) hipLaunchKernelGGL((gemm_strips_kernel_h<128, 64, 2, 2, 2, 1>), dim3(f.max_tiles, f.parts, 4), dim3(256), 0, st, f.ss);
-    else hipLaunchKernelGGL((gemm_strips_kernel_h<64, 64, 2, 2, 1, 1>), dim3(f.max_tiles, f.parts, 4), dim3(256), 0, st, f.ss);
-    DWC_LAUNCH_CHECK();
-    const size_t total = (size_t)B * 2 * pad * (W + H) * (Cin / 4);
-    hipLaunchKernelGGL(fold_ring_kernel_h, dim3((total + 255) / 256), dim3(256), 0, st, (bf16*)dx, (const float*)ws, f.ring_elems[0],
-                       f.ring_elems[0] + f.ring_elems[1], f.ring_elems[0] + f.ring_elems[1] + f.ring_elems[2], f.parts,
-                       f.ring_total, B, H, W, Cin / 4, pad);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    const int rc = launch_strips<true>(f.ss, bm, dim3(f.max_tiles, f.parts, 4), st);
+    if (rc != DWC_OK) return rc;
+    return fold_ring((bf16*)dx, (const float*)ws, f, B, H, W, Cin, pad, st);
 }
 
 int dwc_bf16_conv2d_bwd_data_same(const void* dy, const void* w_dgrad, const void* w_dgrad_t, void* dx, int B, int H, int W,
@@ -1197,11 +949,8 @@ int dwc_bf16_conv2d_bwd_data_image(const void* dy, const void* w_wide, void* dx,
     const int rc = launch_gemm_h(f.g, (const bf16*)w_wide, 0, 1, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, nullptr, 0,
                                  (hipStream_t)stream);
     if (rc != DWC_OK) return rc;
-    const size_t total = (size_t)B * H * W * 2;       // 8 planes = 2 groups of 4 per pixel
-    hipLaunchKernelGGL(fold_reflect_kernel_h, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const bf16*)ws,
-                       (bf16*)dx, B, H, W, 2, pad, f.g.OW * 4);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    // (8 planes = 2 groups of 4 per pixel)
+    return fold_reflect((const bf16*)ws, (bf16*)dx, B, H, W, 2, pad, f.g.OW * 4, (hipStream_t)stream);
 }
 
 /* the same gradient on conv_narrow_bf16.hip (patch staged once per block, taps dealt to the waves): w_frag = the wide bank in
@@ -1215,11 +964,7 @@ int dwc_bf16_conv2d_bwd_data_image_narrow(const void* dy, const void* w_frag, vo
     const int rc = dwc_bf16_conv2d_narrow(dy, w_frag, nullptr, ws, B, H, W, Cout, f.g.OH, f.g.OW, KH, KW + 3, f.g.off_h, f.g.off_w,
                                           DWC_ACT_NONE, 0, stream);
     if (rc != DWC_OK) return rc;
-    const size_t total = (size_t)B * H * W * 2;
-    hipLaunchKernelGGL(fold_reflect_kernel_h, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const bf16*)ws,
-                       (bf16*)dx, B, H, W, 2, pad, f.g.OW * 4);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    return fold_reflect((const bf16*)ws, (bf16*)dx, B, H, W, 2, pad, f.g.OW * 4, (hipStream_t)stream);
 }
 
 size_t dwc_bf16_conv2d_bwd_weight_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {

@@ -56,6 +56,21 @@ struct StripSet {
     size_t part_stride;     // elements between the ring buffers of consecutive parts
 };
 
+// slab[s][(kh,kw,ci)][co] summed over s = 0, 1, 2 ... -> dw[co][ci][kh][kw] (state_dict layout, fp32), real channels only: the
+// plain reduce of every weight-gradient kernel that writes such slabs (im2col fp32 / bf16, bf16 halo)
+__global__ void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ dw, int splits, int K, int N, int Cin,
+                                    int KHW, int cin_real, int cout_real) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)K * N) return;
+    const int co = idx % N;
+    const int k = idx / N;
+    const int ci = k % Cin, tap = k / Cin;
+    if (co >= cout_real || ci >= cin_real) return;
+    float s = 0.f;
+    for (int z = 0; z < splits; ++z) s += slab[(size_t)z * K * N + idx];
+    dw[((size_t)co * cin_real + ci) * KHW + tap] = s;
+}
+
 // Sum of the weight-gradient slabs slab[s][(tap*Cin + ci)][co] over s -> dw[co][ci][tap] for SMALL filters cut into MANY pixel
 // splits (the 7x7 / 4x4 stems on 4-plane images: 12 544 / 4 096 elements, up to a few hundred splits): the element-wise reduce kernels
 // give every element one thread that walks all slabs (89 / 114 us per call on c1, r03 kernel trace).  Here a workgroup owns 32
@@ -102,6 +117,16 @@ inline bool wgrad_reduce_wide(const float* slab, float* dw, int splits, int K, i
     hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, slab, dw, splits, K, N, Cin, KHW,
                        cin_real, cout_real);
     return true;
+}
+
+// (host) the reduce of the im2col weight gradients: the wide form where it takes the shape, otherwise the plain one.  (The two sum
+// in different orders: a caller that launches wgrad_reduce_kernel itself, as the bf16 halo weight gradient does, keeps its own.)
+inline void wgrad_reduce(const float* slab, float* dw, int splits, int K, int N, int Cin, int KHW, int cin_real, int cout_real,
+                         hipStream_t st) {
+    if (wgrad_reduce_wide(slab, dw, splits, K, N, Cin, KHW, cin_real, cout_real, st)) return;
+    const size_t total = (size_t)K * N;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, slab, dw, splits, K, N, Cin, KHW,
+                       cin_real, cout_real);
 }
 
 int kw_magic_for(int KW, int max_tap) {

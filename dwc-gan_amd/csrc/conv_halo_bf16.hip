@@ -61,7 +61,7 @@ __device__ __forceinline__ bf16x8 halo_add8(bf16x8 a, bf16x8 b) {
 // the transposing read (4 consecutive pixels x 16 channels) and LDS read bandwidth is what bounds this kernel, so the unit
 // is walked by PATCH row r: the TW fragments of x row r are read once and used for every kh (against dY row r - kh, kept in
 // a rolling register window of TH fragments): (TW + 1) fragment reads per TH*TW MFMAs instead of TH*TW + 1.
-// Pixel ranges are split over gridDim.y into fp32 slabs [split][tap*Cin + ci][co] that wgrad_halo_reduce sums in a fixed
+// Pixel ranges are split over gridDim.y into fp32 slabs [split][tap*Cin + ci][co] that wgrad_reduce_kernel sums in a fixed
 // order.
 // ------------------------------------------------------------------------------------------
 struct WgradHaloArgs {
@@ -327,20 +327,6 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(WgradHaloArgs a, unsign
 #endif
 }
 
-// slab[s][(kh,kw,ci)][co] summed over s -> dw[co][ci][kh][kw] (state_dict layout, fp32), real channels only
-__global__ void wgrad_halo_reduce_kernel(const float* __restrict__ slab, float* __restrict__ dw, int splits, int K, int N, int Cin,
-                                         int KHW, int cin_real, int cout_real) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)K * N) return;
-    const int co = idx % N;
-    const int k = idx / N;
-    const int ci = k % Cin, tap = k / Cin;
-    if (co >= cout_real || ci >= cin_real) return;
-    float s = 0.f;
-    for (int z = 0; z < splits; ++z) s += slab[(size_t)z * K * N + idx];
-    dw[((size_t)co * cin_real + ci) * KHW + tap] = s;
-}
-
 // BN (channels of dY per workgroup) of a handled shape, 0 otherwise
 // (K == 4 is the stride-2 form: H, W are the dimensions of x, the dY grid is H/2 x W/2)
 int wgrad_halo_bn(int B, int H, int W, int Cin, int Cout, int K) {
@@ -603,7 +589,8 @@ int dwc_bf16_conv2d_wgrad_halo(const void* x, const void* dy, float* dw_oihw, in
     else hipLaunchKernelGGL((wgrad_halo_kernel<5, 64>), grid, dim3(512), 0, st, a);
     DWC_LAUNCH_CHECK();
     const size_t total = (size_t)K * K * Cin * Cout;
-    hipLaunchKernelGGL(wgrad_halo_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const float*)ws, dw_oihw, splits,
+    // (the plain reduce, never wgrad_reduce's wide form: that one sums the slabs in another order)
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const float*)ws, dw_oihw, splits,
                        K * K * Cin, Cout, Cin, K * K, cin_real, cout_real);
     DWC_LAUNCH_CHECK();
     return DWC_OK;

@@ -24,7 +24,7 @@
 
 #include <atomic>
 
-#include "conv_geom.h"
+#include "conv_fold.h"
 
 namespace {
 
@@ -393,22 +393,6 @@ __global__ __launch_bounds__(256) void conv_gemm_strips_kernel(StripSet ss) {
                                            blockIdx.y * ss.part_stride, false, s.oph, s.opw, blockIdx.x, s.tiles);
 }
 
-// dst[i] = act(sum_s part[s][i] + bias[i % N]), fixed summation order
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, float* __restrict__ dst,
-                                                            const float* __restrict__ bias, size_t total4, size_t stride4, int splits,
-                                                            int N, int act) {
-    const int nq = N >> 2;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) {
-        f32x4 s = reinterpret_cast<const f32x4*>(part)[i];
-        for (int z = 1; z < splits; ++z) s += reinterpret_cast<const f32x4*>(part)[(size_t)z * stride4 + i];
-        const int c4 = i % nq;
-        if (bias) s += reinterpret_cast<const f32x4*>(bias)[c4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s[k] = dwc_act_apply(s[k], act, c4 * 4 + k);
-        reinterpret_cast<f32x4*>(dst)[i] = s;
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // weight gradient: dW[k][n] = sum_m A[m][k] * dY[m][n], split over m ("split-K") into slabs
 // ------------------------------------------------------------------------------------------
@@ -619,136 +603,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(Gather g, const float* 
         }
 }
 
-// slab[s][(kh,kw,ci)][co] summed over s -> dw[co][ci][kh][kw] (state_dict layout), real channels only
-__global__ void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ dw, int splits, int K, int N, int Cin,
-                                    int KHW, int cin_real, int cout_real) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)K * N) return;
-    const int co = idx % N;
-    const int k = idx / N;
-    const int ci = k % Cin, tap = k / Cin;
-    if (co >= cout_real || ci >= cin_real) return;
-    float s = 0.f;
-    for (int z = 0; z < splits; ++z) s += slab[(size_t)z * K * N + idx];
-    dw[((size_t)co * cin_real + ci) * KHW + tap] = s;
-}
-
-// reflect-pad adjoint: fold the padded gradient image back onto the un-padded one
-__global__ void fold_reflect_kernel(const float* __restrict__ gp, float* __restrict__ dx, int B, int H, int W, int C4, int pad,
-                                    int Wp) {   // Wp: row pitch of gp in pixels (>= W + 2*pad)
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t total = (size_t)B * H * W * C4;
-    if (idx >= total) return;
-    const int c = idx % C4;
-    size_t r = idx / C4;
-    const int w = r % W;
-    r /= W;
-    const int h = r % H;
-    const int n = r / H;
-    const int Hp = H + 2 * pad;
-    int hs[3], ws[3], nh = 0, nw = 0;
-    hs[nh++] = h + pad;
-    if (h >= 1 && h <= pad) hs[nh++] = pad - h;
-    if (h >= H - 1 - pad && h <= H - 2) hs[nh++] = pad + 2 * (H - 1) - h;
-    ws[nw++] = w + pad;
-    if (w >= 1 && w <= pad) ws[nw++] = pad - w;
-    if (w >= W - 1 - pad && w <= W - 2) ws[nw++] = pad + 2 * (W - 1) - w;
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    const f32x4* g4 = reinterpret_cast<const f32x4*>(gp);
-    for (int a = 0; a < nh; ++a)
-        for (int b = 0; b < nw; ++b) s += g4[((size_t)(n * Hp + hs[a]) * Wp + ws[b]) * C4 + c];
-    reinterpret_cast<f32x4*>(dx)[idx] = s;
-}
-
-// dx (holds the interior of the padded gradient image already: Scatter::crop) += the border ring of gp folded back by the reflect
-// rule; only the pixels a ring pixel folds onto are visited (rows 1..pad and H-1-pad..H-2 whole, columns 1..pad and W-1-pad..W-2
-// of the other rows).
-__global__ __launch_bounds__(256) void fold_band_kernel(const float* __restrict__ gp, float* __restrict__ dx, int B, int H, int W, int C4,
-                                                                 int pad, int Wp) {
-    // one thread per (image, band pixel, channel chunk): per image the 2*pad band rows whole (W pixels each), then the 2*pad band
-    // columns of the H - 2*pad other rows
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const int rows_done = 2 * pad, rest = H - 2 * pad;          // band rows, other rows
-    const int band = rows_done * W + rest * 2 * pad;            // band pixels per image
-    const size_t total = (size_t)B * band * C4;
-    if (idx >= total) return;
-    const int c = idx % C4;
-    size_t r = idx / C4;
-    const int q = r % band;
-    const size_t n = r / band;
-    const int Hp = H + 2 * pad;
-    int h, w;
-    if (q < rows_done * W) {
-        const int br = q / W;
-        w = q - br * W;
-        h = br < pad ? 1 + br : H - 1 - pad + (br - pad);
-    } else {
-        const int q2 = q - rows_done * W;
-        const int hr = q2 / (2 * pad), k = q2 - hr * 2 * pad;
-        // the hr-th row that is NOT a band row: rows 0, pad+1 .. H-2-pad, H-1
-        h = hr == 0 ? 0 : (hr == rest - 1 ? H - 1 : pad + hr);
-        w = k < pad ? 1 + k : W - 1 - pad + (k - pad);
-    }
-    int hs[3], ws[3], nh = 0, nw = 0;
-    hs[nh++] = h + pad;
-    if (h >= 1 && h <= pad) hs[nh++] = pad - h;
-    if (h >= H - 1 - pad && h <= H - 2) hs[nh++] = pad + 2 * (H - 1) - h;
-    ws[nw++] = w + pad;
-    if (w >= 1 && w <= pad) ws[nw++] = pad - w;
-    if (w >= W - 1 - pad && w <= W - 2) ws[nw++] = pad + 2 * (W - 1) - w;
-    if (nh * nw == 1) return;
-    const size_t o = ((n * H + h) * (size_t)W + w) * C4 + c;
-    f32x4 s = reinterpret_cast<const f32x4*>(dx)[o];
-    const f32x4* g4 = reinterpret_cast<const f32x4*>(gp);
-    for (int a = 0; a < nh; ++a)
-        for (int b = 0; b < nw; ++b) {
-            if (a == 0 && b == 0) continue;               // the pixel's own (interior) value is in dx already
-            s += g4[((n * Hp + hs[a]) * (size_t)Wp + ws[b]) * C4 + c];
-        }
-    reinterpret_cast<f32x4*>(dx)[o] = s;
-}
-
-// Weight layouts streamed by conv_gemm_kernel: one row per GEMM column n, K contiguous and
-// zero-padded to a multiple of 32 ("[N][Kp]"), so the B tile is staged exactly like the A tile.
-//   forward : row = co, k = (kh*KW + kw)*cin_pad + ci                      value W[co][ci][kh][kw]
-//   dgrad s1: row = ci, k = (kh'*KW + kw')*cout_pad + co                   value W[co][ci][KH-1-kh'][KW-1-kw']
-//   dgrad s2: [class ph*2+pw] row = ci, k = (th*2 + tw)*cout_pad + co      value W[co][ci][ph+2th][pw+2tw]  (4x4 kernel)
-__global__ void weight_prepare_fwd_kernel(const float* __restrict__ w, float* __restrict__ out, int Cout, int Cin, int KHW,
-                                          int cout_pad, int cin_pad, int Kp) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)cout_pad * Kp) return;
-    const int k = idx % Kp, co = idx / Kp;
-    const int ci = k % cin_pad, tap = k / cin_pad;
-    float v = 0.f;
-    if (co < Cout && ci < Cin && tap < KHW) v = w[((size_t)co * Cin + ci) * KHW + tap];
-    out[idx] = v;
-}
-
-__global__ void weight_prepare_dgrad_kernel(const float* __restrict__ w, float* __restrict__ out, int Cout, int Cin, int KH, int KW,
-                                            int stride, int cout_pad, int cin_pad, int Kp) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t per_class = (size_t)cin_pad * Kp;
-    const int classes = stride == 1 ? 1 : 4;
-    if (idx >= per_class * classes) return;
-    const int cls = idx / per_class;
-    const size_t r = idx % per_class;
-    const int k = r % Kp, ci = r / Kp;
-    const int co = k % cout_pad, tapo = k / cout_pad;
-    int kh, kw;
-    bool ok = co < Cout && ci < Cin;
-    if (stride == 1) {
-        ok = ok && tapo < KH * KW;
-        kh = KH - 1 - tapo / KW;
-        kw = KW - 1 - tapo % KW;
-    } else {
-        ok = ok && tapo < 4;
-        kh = (cls >> 1) + 2 * (tapo >> 1);
-        kw = (cls & 1) + 2 * (tapo & 1);
-    }
-    out[idx] = ok ? w[((size_t)co * Cin + ci) * KH * KW + kh * KW + kw] : 0.f;
-}
-
-
 
 template <int BM, int BN, int WM, int WN, int TM, int TN, bool X3 = false>
 void launch_variant(const Gather& g, const float* w, size_t wcs, int classes, const Scatter& o, const float* bias, int act,
@@ -801,17 +655,49 @@ int launch_gemm(const Gather& g, const float* w, size_t w_class_stride, int clas
     else if (p.bm == 64 && p.bn == 64) launch_variant<64, 64, 2, 2, 1, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
     else launch_variant<128, 32, 4, 1, 1, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
     DWC_LAUNCH_CHECK();
-    if (p.splits > 1) {
-        const size_t total4 = dst_elems / 4;
-        size_t blocks = (total4 + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)ws, final_dst, bias, total4,
-                           total4, p.splits, o.N, act);
-        DWC_LAUNCH_CHECK();
-    }
+    if (p.splits > 1) return splitk_reduce((const float*)ws, final_dst, bias, dst_elems, p.splits, o.N, act, st);
     return DWC_OK;
 }
 
+// The ring strips of a data gradient (same_dgrad_geom / s2_ring_geom built with row tiles of `bm`).  Only the 64-row tile exists
+// here: strip_bm(..., half = false) never asks for another.
+int launch_strips(const StripSet& ss, int bm, dim3 grid, hipStream_t st) {
+    if (bm != 64) return DWC_EINVAL;
+    if (gemm_x3_on(ss.s[0].g.K)) hipLaunchKernelGGL((conv_gemm_strips_kernel<64, 64, 2, 2, 1, 1, true>), grid, dim3(256), 0, st, ss);
+    else hipLaunchKernelGGL((conv_gemm_strips_kernel<64, 64, 2, 2, 1, 1>), grid, dim3(256), 0, st, ss);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+
+int wgrad_launch(const FwdGeom& f, const float* dy, float* dw_oihw, int Cin, int Cout, int KHW, int cin_real, int cout_real,
+                 void* ws, size_t ws_bytes, hipStream_t st) {
+    const Gather& g = f.g;
+    int splits, chunk;
+    wgrad_plan(g.M, g.K, Cout, &splits, &chunk);
+    if (!ws || ws_bytes < (size_t)splits * g.K * Cout * sizeof(float)) return DWC_EWORKSPACE;
+    float* slab = (float*)ws;
+    const int tk = (g.K + 127) / 128;
+    if (wgrad_x3_on()) {
+        if (Cout > 64)
+            hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2, true>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
+                               Cout, slab, chunk);
+        else if (Cout > 32)
+            hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+        else
+            hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+    } else if (Cout > 64) {
+        hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
+                           Cout, slab, chunk);
+    } else if (Cout > 32) {
+        hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+    } else {
+        hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+    }
+    DWC_LAUNCH_CHECK();
+    wgrad_reduce(slab, dw_oihw, splits, g.K, Cout, Cin, KHW, cin_real, cout_real, st);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
 
 }  // namespace
 
@@ -828,20 +714,13 @@ int dwc_x3_gemm_mode(int mode) {
 }
 
 size_t dwc_weight_prepared_elems(int Cout, int Cin, int KH, int KW, int stride, int cout_pad, int cin_pad, int for_dgrad) {
-    if (!for_dgrad) return (size_t)cout_pad * ((KH * KW * cin_pad + BK - 1) / BK * BK);
-    if (stride == 1) return (size_t)cin_pad * ((KH * KW * cout_pad + BK - 1) / BK * BK);
-    return (size_t)4 * cin_pad * ((4 * cout_pad + BK - 1) / BK * BK);
+    return weight_prepared_elems(KH, KW, stride, cout_pad, cin_pad, for_dgrad, BK);
 }
 
 int dwc_weight_prepare_fwd(const float* w, float* out, int Cout, int Cin, int KH, int KW, int cout_pad, int cin_pad,
                            void* stream) {
     if (cout_pad < Cout || cin_pad < Cin) return DWC_EINVAL;
-    const int Kp = (KH * KW * cin_pad + BK - 1) / BK * BK;
-    const size_t total = (size_t)cout_pad * Kp;
-    hipLaunchKernelGGL(weight_prepare_fwd_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin,
-                       KH * KW, cout_pad, cin_pad, Kp);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    return weight_prepare_fwd(w, out, Cout, Cin, KH, KW, cout_pad, cin_pad, BK, (hipStream_t)stream);
 }
 
 int dwc_weight_prepare_dgrad(const float* w, float* out, int Cout, int Cin, int KH, int KW, int stride, int cout_pad,
@@ -849,12 +728,7 @@ int dwc_weight_prepare_dgrad(const float* w, float* out, int Cout, int Cin, int 
     if (cout_pad < Cout || cin_pad < Cin) return DWC_EINVAL;
     if (stride == 2 && !(KH == 4 && KW == 4)) return DWC_EINVAL;
     if (stride != 1 && stride != 2) return DWC_EINVAL;
-    const int Kp = ((stride == 1 ? KH * KW : 4) * cout_pad + BK - 1) / BK * BK;
-    const size_t total = (size_t)(stride == 1 ? 1 : 4) * cin_pad * Kp;
-    hipLaunchKernelGGL(weight_prepare_dgrad_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, out, Cout,
-                       Cin, KH, KW, stride, cout_pad, cin_pad, Kp);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    return weight_prepare_dgrad(w, out, Cout, Cin, KH, KW, stride, cout_pad, cin_pad, BK, (hipStream_t)stream);
 }
 
 size_t dwc_conv2d_fwd_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
@@ -903,39 +777,6 @@ int dwc_conv2d_fwd_ex(const float* x, const float* w_prepared, const float* bias
     return launch_gemm(f.g, w_prepared, 0, 1, f.o, bias, act, f.dst_elems, nullptr, 0, (hipStream_t)stream);
 }
 
-static int wgrad_launch(const FwdGeom& f, const float* dy, float* dw_oihw, int Cin, int Cout, int KHW, int cin_real, int cout_real,
-                        void* ws, size_t ws_bytes, hipStream_t st) {
-    const Gather& g = f.g;
-    int splits, chunk;
-    wgrad_plan(g.M, g.K, Cout, &splits, &chunk);
-    if (!ws || ws_bytes < (size_t)splits * g.K * Cout * sizeof(float)) return DWC_EWORKSPACE;
-    float* slab = (float*)ws;
-    const int tk = (g.K + 127) / 128;
-    if (wgrad_x3_on()) {
-        if (Cout > 64)
-            hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2, true>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
-                               Cout, slab, chunk);
-        else if (Cout > 32)
-            hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-        else
-            hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-    } else if (Cout > 64) {
-        hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
-                           Cout, slab, chunk);
-    } else if (Cout > 32) {
-        hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-    } else {
-        hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-    }
-    DWC_LAUNCH_CHECK();
-    const size_t total = (size_t)g.K * Cout;
-    if (!wgrad_reduce_wide(slab, dw_oihw, splits, g.K, Cout, Cin, KHW, cin_real, cout_real, st))
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, slab, dw_oihw, splits, g.K, Cout, Cin, KHW,
-                           cin_real, cout_real);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
-}
-
 size_t dwc_conv2d_bwd_weight_ex_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride_h, int stride_w,
                                          int pad_h, int pad_w) {
     FwdGeom f;
@@ -962,84 +803,21 @@ size_t dwc_conv2d_bwd_data_ws_bytes(int B, int H, int W, int Cin, int Cout, int 
 
 int dwc_reflect_pad_adjoint(const float* dxp, float* dx, int B, int H, int W, int C, int pad, void* stream) {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || pad < 0 || pad >= H || pad >= W) return DWC_EINVAL;
-    const size_t total = (size_t)B * H * W * (C / 4);
-    hipLaunchKernelGGL(fold_reflect_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, dxp, dx, B, H, W, C / 4,
-                       pad, W + 2 * pad);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    return fold_reflect(dxp, dx, B, H, W, C / 4, pad, W + 2 * pad, (hipStream_t)stream);
 }
 
 /* dx (already holding the interior of the padded gradient image dxp [B][H+2pad][W+2pad][C]) += the border ring of dxp folded back by
  * the reflect rule; only the band of dx a ring pixel folds onto is visited (fp32 twin of dwc_bf16_reflect_pad_adjoint_band). */
 int dwc_reflect_pad_adjoint_band(const float* dxp, float* dx, int B, int H, int W, int C, int pad, void* stream) {
     if (!dxp || !dx || B <= 0 || C <= 0 || (C & 3) || pad <= 0 || H < 2 * pad + 2 || W < 2 * pad + 2) return DWC_EINVAL;
-    const int C4 = C / 4;
-    const size_t band_items = (size_t)B * (2 * pad * W + (H - 2 * pad) * 2 * pad) * C4;
-    hipLaunchKernelGGL(fold_band_kernel, dim3((unsigned)((band_items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dxp, dx, B, H, W, C4, pad,
-                       W + 2 * pad);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    return fold_band(dxp, dx, B, H, W, C, pad, (hipStream_t)stream);
 }
 
 /* The same for a padded gradient image whose rows are `pitch` >= W + 2*pad pixels apart (the 8-pixel-group grid of
  * dwc_x3_conv2d_narrow's image gradient). */
 int dwc_reflect_pad_adjoint_pitch(const float* dxp, float* dx, int B, int H, int W, int C, int pad, int pitch, void* stream) {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || pad < 0 || pad >= H || pad >= W || pitch < W + 2 * pad) return DWC_EINVAL;
-    const size_t total = (size_t)B * H * W * (C / 4);
-    hipLaunchKernelGGL(fold_reflect_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, dxp, dx, B, H, W, C / 4,
-                       pad, pitch);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
-}
-
-// dx += the border ring of the padded gradient image, folded back by the reflect rule.  dx already holds the interior;
-// the ring lives in four strips: top/bottom [B][pad][Wp][C], left/right [B][H][pad][C], `parts` copies `part_stride`
-// apart (partial sums over K, added in order).  Only the bands of dx that receive something are visited: per image
-// 2*pad rows x W pixels (rows 1..pad, H-1-pad..H-2) then 2*pad columns x H pixels (skipping the rows already done).
-__global__ void fold_ring_kernel(float* __restrict__ dx, const float* __restrict__ ring, size_t off_bottom, size_t off_left,
-                                 size_t off_right, int parts, size_t part_stride, int B, int H, int W, int C4, int pad) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int band = 2 * pad * (W + H);
-    const size_t total = (size_t)B * band * C4;
-    if (idx >= total) return;
-    const int c = idx % C4;
-    size_t r = idx / C4;
-    const int q = r % band;
-    const int n = r / band;
-    int h, w;
-    if (q < 2 * pad * W) {
-        const int br = q / W;
-        w = q - br * W;
-        h = br < pad ? 1 + br : H - 1 - pad + (br - pad);
-    } else {
-        const int q2 = q - 2 * pad * W, bc = q2 / H;
-        h = q2 - bc * H;
-        w = bc < pad ? 1 + bc : W - 1 - pad + (bc - pad);
-        if ((h >= 1 && h <= pad) || (h >= H - 1 - pad && h <= H - 2)) return;   // covered by the row bands
-    }
-    if (h < 0 || h >= H || w < 0 || w >= W) return;
-    const int Wp = W + 2 * pad;
-    int hs[3], ws[3], nh = 0, nw = 0;
-    hs[nh++] = h + pad;
-    if (h >= 1 && h <= pad) hs[nh++] = pad - h;
-    if (h >= H - 1 - pad && h <= H - 2) hs[nh++] = pad + 2 * (H - 1) - h;
-    ws[nw++] = w + pad;
-    if (w >= 1 && w <= pad) ws[nw++] = pad - w;
-    if (w >= W - 1 - pad && w <= W - 2) ws[nw++] = pad + 2 * (W - 1) - w;
-    f32x4* out = reinterpret_cast<f32x4*>(dx) + ((size_t)(n * H + h) * W + w) * C4 + c;
-    f32x4 s = *out;
-    for (int a = 0; a < nh; ++a)
-        for (int b = 0; b < nw; ++b) {
-            if (a == 0 && b == 0) continue;
-            const int rh = hs[a], rw = ws[b];
-            size_t e;   // element offset inside one part's ring
-            if (rh < pad) e = ((size_t)(n * pad + rh) * Wp + rw) * C4;
-            else if (rh >= pad + H) e = off_bottom / 4 + ((size_t)(n * pad + rh - pad - H) * Wp + rw) * C4;
-            else if (rw < pad) e = off_left / 4 + ((size_t)(n * H + rh - pad) * pad + rw) * C4;
-            else e = off_right / 4 + ((size_t)(n * H + rh - pad) * pad + rw - pad - W) * C4;
-            for (int p = 0; p < parts; ++p) s += reinterpret_cast<const f32x4*>(ring + p * part_stride)[e + c];
-        }
-    *out = s;
+    return fold_reflect(dxp, dx, B, H, W, C / 4, pad, pitch, (hipStream_t)stream);
 }
 
 
@@ -1059,7 +837,7 @@ int dwc_conv2d_bwd_data_same(const float* dy, const float* w_dgrad, const float*
     return same_dgrad_run(dy, w_dgrad, w_dgrad_t, dx, B, H, W, Cin, Cout, KH, KW, pad, ws, ws_bytes, stream, false);
 }
 
-// Only the border ring: dx must already hold the interior (e.g. from dwc_conv2d_wino with the zero rule).
+// Only the border ring: dx must already hold the interior (dwc_x3_ / dwc_h2_conv2d_same_add_ws with the zero rule).
 int dwc_conv2d_bwd_data_ring(const float* dy, const float* w_dgrad, const float* w_dgrad_t, float* dx, int B, int H, int W,
                              int Cin, int Cout, int KH, int KW, int pad, void* ws, size_t ws_bytes, void* stream) {
     return same_dgrad_run(dy, w_dgrad, w_dgrad_t, dx, B, H, W, Cin, Cout, KH, KW, pad, ws, ws_bytes, stream, true);
@@ -1078,21 +856,9 @@ static int same_dgrad_run(const float* dy, const float* w_dgrad, const float* w_
                              ws_bytes - ring_bytes, st);
         if (rc != DWC_OK) return rc;
     }
-    const dim3 sgrid(f.max_tiles, f.parts, 4);
-    if (gemm_x3_on(f.ss.s[0].g.K)) {
-        if (bm == 128) hipLaunchKernelGGL((conv_gemm_strips_kernel<128, 64, 2, 2, 2, 1, true>), sgrid, dim3(256), 0, st, f.ss);
-        else hipLaunchKernelGGL((conv_gemm_strips_kernel<64, 64, 2, 2, 1, 1, true>), sgrid, dim3(256), 0, st, f.ss);
-    } else {
-        if (bm == 128) hipLaunchKernelGGL((conv_gemm_strips_kernel<128, 64, 2, 2, 2, 1>), sgrid, dim3(256), 0, st, f.ss);
-        else hipLaunchKernelGGL((conv_gemm_strips_kernel<64, 64, 2, 2, 1, 1>), sgrid, dim3(256), 0, st, f.ss);
-    }
-    DWC_LAUNCH_CHECK();
-    const size_t total = (size_t)B * 2 * pad * (W + H) * (Cin / 4);
-    hipLaunchKernelGGL(fold_ring_kernel, dim3((total + 255) / 256), dim3(256), 0, st, dx, (const float*)ws, f.ring_elems[0],
-                       f.ring_elems[0] + f.ring_elems[1], f.ring_elems[0] + f.ring_elems[1] + f.ring_elems[2], f.parts,
-                       f.ring_total, B, H, W, Cin / 4, pad);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    const int rc = launch_strips(f.ss, bm, dim3(f.max_tiles, f.parts, 4), st);
+    if (rc != DWC_OK) return rc;
+    return fold_ring(dx, (const float*)ws, f, B, H, W, Cin, pad, st);
 }
 
 
@@ -1109,11 +875,7 @@ int dwc_conv2d_bwd_data_image(const float* dy, const float* w_wide, float* dx, i
     if (!ws || ws_bytes < f.dst_elems * sizeof(float)) return DWC_EWORKSPACE;
     const int rc = launch_gemm(f.g, w_wide, 0, 1, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, nullptr, 0, (hipStream_t)stream);
     if (rc != DWC_OK) return rc;
-    const size_t total = (size_t)B * H * W;
-    hipLaunchKernelGGL(fold_reflect_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)ws, dx, B, H,
-                       W, 1, pad, f.g.OW * 8);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    return fold_reflect((const float*)ws, dx, B, H, W, 1, pad, f.g.OW * 8, (hipStream_t)stream);
 }
 
 int dwc_conv2d_bwd_data(const float* dy, const float* w_dgrad, float* dxp, int B, int H, int W, int Cin, int Cout, int KH,
@@ -1140,12 +902,7 @@ int dwc_conv2d_bwd_data_fold(const float* dy, const float* w_dgrad, float* dxp, 
     int rc = launch_gemm(f.g, w_dgrad, f.wcs, f.classes, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, ws, ws_bytes, st);
     if (rc != DWC_OK) return rc;
     if (!direct) return dwc_reflect_pad_adjoint(dxp, dx, B, H, W, Cin, pad, stream);
-    const int C4 = Cin / 4;
-    const size_t band_items = (size_t)B * (2 * pad * W + (H - 2 * pad) * 2 * pad) * C4;
-    hipLaunchKernelGGL(fold_band_kernel, dim3((unsigned)((band_items + 255) / 256)), dim3(256), 0, st, (const float*)dxp, dx, B, H, W, C4, pad,
-                       W + 2 * pad);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    return fold_band((const float*)dxp, dx, B, H, W, Cin, pad, st);
 }
 
 /* Border ring + fold of the data gradient of a 4x4 stride-2 reflect-pad-1 convolution whose INTERIOR (the H x W pixels of dx)
@@ -1160,21 +917,9 @@ int dwc_conv2d_bwd_data_s2_ring(const float* dy, const float* w_dgrad, float* dx
         !s2_ring_geom(dy, w_dgrad, dxp, sizeof(float), B, H, W, Cin, Cout, &f, 32, 2, bm))
         return DWC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 sgrid(f.max_tiles, 1, 8);
-    if (gemm_x3_on(f.ss.s[0].g.K)) {
-        if (bm == 128) hipLaunchKernelGGL((conv_gemm_strips_kernel<128, 64, 2, 2, 2, 1, true>), sgrid, dim3(256), 0, st, f.ss);
-        else hipLaunchKernelGGL((conv_gemm_strips_kernel<64, 64, 2, 2, 1, 1, true>), sgrid, dim3(256), 0, st, f.ss);
-    } else {
-        if (bm == 128) hipLaunchKernelGGL((conv_gemm_strips_kernel<128, 64, 2, 2, 2, 1>), sgrid, dim3(256), 0, st, f.ss);
-        else hipLaunchKernelGGL((conv_gemm_strips_kernel<64, 64, 2, 2, 1, 1>), sgrid, dim3(256), 0, st, f.ss);
-    }
-    DWC_LAUNCH_CHECK();
-    const int C4 = Cin / 4;
-    const size_t band_items = (size_t)B * (2 * W + (H - 2) * 2) * C4;
-    hipLaunchKernelGGL(fold_band_kernel, dim3((unsigned)((band_items + 255) / 256)), dim3(256), 0, st, (const float*)dxp, dx, B, H, W, C4, 1,
-                       W + 2);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    const int rc = launch_strips(f.ss, bm, dim3(f.max_tiles, 1, 8), st);
+    if (rc != DWC_OK) return rc;
+    return fold_band((const float*)dxp, dx, B, H, W, Cin, 1, st);
 }
 
 size_t dwc_conv2d_bwd_weight_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
@@ -1189,36 +934,7 @@ int dwc_conv2d_bwd_weight(const float* x, const float* dy, float* dw_oihw, int B
     FwdGeom f;
     if (!fwd_geom(x, nullptr, B, H, W, Cin, Cout, KH, KW, stride, pad, &f)) return DWC_EINVAL;
     if (cin_real > Cin || cout_real > Cout) return DWC_EINVAL;
-    if (!ws || ws_bytes < dwc_conv2d_bwd_weight_ws_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad)) return DWC_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const Gather& g = f.g;
-    int splits, chunk;
-    wgrad_plan(g.M, g.K, Cout, &splits, &chunk);
-    float* slab = (float*)ws;
-    const int tk = (g.K + 127) / 128;
-    if (wgrad_x3_on()) {
-        if (Cout > 64)
-            hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2, true>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
-                               Cout, slab, chunk);
-        else if (Cout > 32)
-            hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-        else
-            hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-    } else if (Cout > 64) {
-        hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
-                           Cout, slab, chunk);
-    } else if (Cout > 32) {
-        hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-    } else {
-        hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-    }
-    DWC_LAUNCH_CHECK();
-    const size_t total = (size_t)g.K * Cout;
-    if (!wgrad_reduce_wide(slab, dw_oihw, splits, g.K, Cout, Cin, KH * KW, cin_real, cout_real, st))
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, slab, dw_oihw, splits, g.K, Cout, Cin,
-                           KH * KW, cin_real, cout_real);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+    return wgrad_launch(f, dy, dw_oihw, Cin, Cout, KH * KW, cin_real, cout_real, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -16,7 +16,7 @@ namespace {
 
 typedef __bf16 bf16;
 
-// fwd / dgrad element of the [rows][Kp] im2col layout (conv_igemm.hip: weight_prepare_fwd_kernel / _dgrad_kernel)
+// fwd / dgrad element of the [rows][Kp] im2col layout (conv_fold.h: weight_prepare_fwd_kernel / _dgrad_kernel)
 __device__ __forceinline__ float im2col_elem(const dwc_refresh_desc& d, size_t idx, bool dgrad) {
     const float* w = d.src;
     if (!dgrad) {
