@@ -200,9 +200,12 @@ SIGNATURES = {
     "dwc_sn_epilogue_bwd": (c_int, [c_fp] * 7 + [c_int] * 4 + [c_fp, c_sz, c_fp, c_u, c_fp]),
     "dwc_bf16_sn_epilogue_bwd": (c_int, [c_fp] * 7 + [c_int] * 4 + [c_fp, c_sz, c_fp]),
     "dwc_sn_weight_grad": (c_int, [c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_fp] + [c_int] * 4 + [c_fp]),
+    "dwc_grad_penalty_fwd": (c_int, [c_fp] * 4 + [c_int] * 5 + [c_fp]),
+    "dwc_grad_penalty_scale": (c_int, [c_fp] * 4 + [c_int] * 4 + [c_fp]),
+    "dwc_src_head_seed": (c_int, [c_fp] * 3 + [c_int] * 3 + [c_fp]),
 }
 
-ABI_VERSION = 8                # DWC_ABI_VERSION of include/dwcgan_hip.h
+ABI_VERSION = 9                # DWC_ABI_VERSION of include/dwcgan_hip.h
 EINVAL = -1
 _ERRORS = {-1: "DWC_EINVAL (unsupported shape/argument)", -2: "DWC_EWORKSPACE (scratch too small)",
            -3: "DWC_ELAUNCH (kernel launch failed)"}

@@ -599,6 +599,10 @@ X3_WGRAD_HALO3 = int(os.environ.get("DWC_X3_WGRAD_HALO3", "1"))   # 0: 3x3 weigh
 PINNED_STAGE = int(os.environ.get("DWC_PINNED_STAGE", "1"))        # small host->device tables through pinned staging (0: pageable copies, which wait for the stream)
 ZERO_GRAD_BY_FLAG = int(os.environ.get("DWC_ZERO_GRAD_FLAG", "1"))   # biases whose gradient is identically zero: flagged, not filled (0: torch.zeros per use)
 RING_FUSED = int(os.environ.get("DWC_RING_FUSED", "1"))   # stride-1 data gradients: border ring inside the halo launch (0: strip GEMM + fold launches)
+# gradient / R1 penalties of the D step on the closed-form second derivative over the HIP convolutions (hipdwc.penalty) where the
+# discriminator allows it (MsImageDis.penalty_hip_ok); 0: always torch's double backward (MsImageDis.forward_src_scale0_torch).
+# Opt-in: neither form has been timed at the c1 / c2 shapes yet (benchmarks/penalty_overhead.py).
+PENALTY_HIP = int(os.environ.get("DWC_PENALTY_HIP", "0"))
 S2DGRAD_MIN_WGS = 192        # below this many workgroups (4 classes x blocks x 64-channel tiles) the im2col GEMM keeps the layer
 
 

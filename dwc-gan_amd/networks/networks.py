@@ -445,6 +445,22 @@ class MsImageDis(nn.Module):
                 h = blk._torch_act(h)
         return F.conv2d(h, self.cnns_src[0].weight, self.cnns_src[0].bias)
 
+    def penalty_hip_ok(self):
+        """Whether the penalties of this discriminator have the closed-form second derivative of hipdwc.penalty: no normalisation
+        (the rank-one sigma term of 'sn' is not built), reflect padding, a piecewise-linear activation, channel counts the
+        pointwise passes take."""
+        from hipdwc import penalty
+        blocks = list(self.cnns_feat[0])
+        return (self.norm == "none" and self.pad_type == "reflect" and self.activ in penalty.ACTS
+                and penalty.supported([blk.conv.weight for blk in blocks], [blk.act_kind for blk in blocks]))
+
+    def src_grad_penalty(self, x, mode):
+        """The gradient penalty (mode "gp") / R1 penalty (mode "r1") of the first scale's 'src' map at x -- the value of
+        Solver.gradient_penalty / r1_penalty on forward_src_scale0_torch(x) -- on the HIP kernels, differentiable w.r.t. this
+        scale's convolution weights (hipdwc.penalty).  x: [B, 3, H, W] fp32 or an fp32 NHWC4 image buffer."""
+        from hipdwc import penalty
+        return penalty.src_grad_penalty(self, x, mode)
+
     def _classification_loss(self, logit, target, dataset="CelebA"):
         if dataset in ("CelebA", "CUB200"):
             return F.binary_cross_entropy_with_logits(logit, target, reduction="mean")

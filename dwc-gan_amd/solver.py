@@ -295,18 +295,28 @@ class Solver(nn.Module):
                 self.dis.dis_loss_terms(o[pairs[1][0]], o[pairs[1][1]], label_src, gw, cw)
         self.loss_dis_all = self.loss_dis
         # Gradient / R1 penalties (reference solver.py:337-350; gp_w 0 and use_r1 False in the shipped configuration).  Both differentiate
-        # the first scale's src map w.r.t. its INPUT and then that gradient w.r.t. D's weights: a double backward, taken on stock torch
-        # device ops over the same parameters (MsImageDis.forward_src_scale0_torch) -- the HIP Functions are once-differentiable.
+        # the first scale's src map w.r.t. its INPUT and then that gradient w.r.t. D's weights.  The HIP Functions are once-differentiable:
+        # with ops.PENALTY_HIP, and a discriminator whose second derivative has the closed form (MsImageDis.penalty_hip_ok: norm none,
+        # reflect padding, lrelu / relu / none), the penalty is one Function over the HIP convolutions (hipdwc.penalty); anything else
+        # takes torch's double backward on stock device ops over the same parameters (MsImageDis.forward_src_scale0_torch).
         # The reference adds them IN PLACE to the tensor both names refer to (`self.loss_dis_all = self.loss_dis; ... += ...`): loss_dis
         # reads the penalised value afterwards too; kept.
+        hip_penalty = bool(ops.PENALTY_HIP) and self.dis.penalty_hip_ok()
         if configs["gp_w"] > 0.0:
             alpha = host.noise().rand((x_real.size(0), 1, 1, 1), x_real.device)
-            x_hat = (alpha * x_real.detach()[:, :3].float() + (1 - alpha) * fakes[:B, :3].detach().float()).requires_grad_(True)
-            self.loss_gp = self.gradient_penalty(self.dis.forward_src_scale0_torch(x_hat), x_hat) * configs["gp_w"]
+            x_hat = alpha * x_real.detach()[:, :3].float() + (1 - alpha) * fakes[:B, :3].detach().float()
+            if hip_penalty:
+                self.loss_gp = self.dis.src_grad_penalty(x_hat, "gp") * configs["gp_w"]
+            else:
+                x_hat.requires_grad_(True)
+                self.loss_gp = self.gradient_penalty(self.dis.forward_src_scale0_torch(x_hat), x_hat) * configs["gp_w"]
             self.loss_dis_all = self.loss_dis = self.loss_dis_all + self.loss_gp
         if configs["use_r1"] and (iters + 1) % self.d_reg_every == 0:
-            x_r = x_real.detach()[:, :3].float().requires_grad_(True)
-            self.loss_r1 = self.r1_penalty(self.dis.forward_src_scale0_torch(x_r), x_r) * 10. / 2
+            if hip_penalty:     # (the fp32 image buffer of the D pass when there is one; bf16 mode packs x_real again, in fp32)
+                self.loss_r1 = self.dis.src_grad_penalty(x4 if x4.dtype == torch.float32 else x_real.detach()[:, :3], "r1") * 10. / 2
+            else:
+                x_r = x_real.detach()[:, :3].float().requires_grad_(True)
+                self.loss_r1 = self.r1_penalty(self.dis.forward_src_scale0_torch(x_r), x_r) * 10. / 2
             self.loss_dis_all = self.loss_dis = self.loss_dis_all + self.loss_r1
         self.loss_dis_all.backward()
         self._sync_grads("dis")             # data parallel: average D's gradients over the ranks

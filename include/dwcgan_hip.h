@@ -48,7 +48,7 @@ extern "C" {
 /* Version of this C ABI: bumped with every change of an entry point's signature or of a structure passed through it (r05: 5 --
  * dwc_weight_refresh_multi gained has_h2 / epoch, the dwc_h2_* / dwc_*_amax entry points).  A binding must refuse a library that
  * reports another number: symbols alone do not tell a changed argument list (hipdwc/_lib.py does). */
-#define DWC_ABI_VERSION 8
+#define DWC_ABI_VERSION 9
 int dwc_version(void);
 /* The fp32 im2col kernels (dwc_conv2d_fwd / _bwd_data* / _bwd_weight*, ring strips) take their inner products as exact three-way
  * bf16 split products on the bf16 matrix cores by default (r04; fp32 operands, results and accumulation -- see
@@ -688,6 +688,24 @@ int dwc_bf16_sn_epilogue_bwd(const void* dy, const void* Z, const float* r, cons
  * u_s = U + s * u_stride, v_s = V + s * v_stride (stride 0: the same pair for every s). */
 int dwc_sn_weight_grad(const float* U, int u_stride, const float* V, int v_stride, const float* r, const float* c, float* dw, int S,
                        int cout, int k, int accumulate, void* stream);
+
+/* ---- gradient / R1 penalty of the discriminator (reference solver.py:291-315; csrc/penalty.hip) ----------------------
+ * g: the gradient of sum(src map) w.r.t. the input image, fp32 [B][pixels][planes] of which the first real_planes planes count (the
+ * NHWC4 image: planes 4, real_planes 3; the other planes are never read into a sum).  q_n = sum over pixels and real planes of g^2;
+ *   DWC_PENALTY_GP: P = mean_n (sqrt(q_n) - 1)^2,  k_n = 2 (sqrt(q_n) - 1) / (B sqrt(q_n)), k_n = 0 where q_n = 0
+ *   DWC_PENALTY_R1: P = mean_n q_n^2,              k_n = 4 q_n / B           (the reference squares the squared norm)
+ * so that dP/dg = k_n g_n.  q, k: [B], out: [1].  One workgroup per sample and one closing workgroup, sums in a fixed order
+ * (no atomics: bit-identical run to run). */
+#define DWC_PENALTY_GP 0
+#define DWC_PENALTY_R1 1
+int dwc_grad_penalty_fwd(const float* g, float* q, float* k, float* out, int B, int pixels, int planes, int real_planes, int mode,
+                         void* stream);
+/* ghat = dout[0] * k_n * g on the real planes, 0 on the others; dout: one fp32 value in DEVICE memory. */
+int dwc_grad_penalty_scale(const float* g, const float* k, const float* dout, float* ghat, int B, int pixels, int planes,
+                           int real_planes, void* stream);
+/* d[r][c] = w_s[c] * act'(a[r][c]) (act in {none, relu, lrelu}, the derivative read off the activation OUTPUT a): the gradient of
+ * the sum of the 1x1 'src' head's map w.r.t. the pre-activation of the layer below it, in one pass.  C a multiple of 4. */
+int dwc_src_head_seed(const float* a, const float* w_s, float* d, int rows, int C, int act, void* stream);
 
 #ifdef __cplusplus
 }
