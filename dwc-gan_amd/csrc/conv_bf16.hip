@@ -17,7 +17,7 @@
 // ds_read_b64_tr_b16 (a 4-pixel x 16-channel block per 16 lanes, delivered channel-major).
 #include <type_traits>
 
-#include "conv_fold.h"
+#include "conv_im2col_entry.h"
 
 namespace {
 
@@ -651,307 +651,117 @@ void launch_variant_h(const Gather& g, const bf16* w, size_t wcs, int classes, c
                            dim3(64 * WM * WN), 0, st, g, w, wcs, o, bias, act, tiles_n, p.kt_per_split, part_stride);
 }
 
-// Tile choice for the bf16 kernels: the fp32 planner's candidates plus the 8-wave 256-row tiles (one workgroup per CU,
-// 128 KiB / 96 KiB of LDS).  At bf16 MFMA rates the 128x128 tile is bound by what a CU can pull out of L2 into LDS
-// (32 KB per 64-deep slab) and by LDS read bandwidth (one ds_read_b128 per MFMA with 64x64 wave tiles); a 256x256 tile
-// halves both per flop (128x64 wave tiles: 0.75 reads per MFMA), a 256x128 tile saves a quarter.  `f` = measured relative
-// rate at full residency (kernel_bench_bf16, r02), the cost model is plan_gemm's (rounds of resident workgroups).
-Plan plan_gemm_h(int M, int N, int K, int classes) {
-    struct Cand { int bm, bn, resident; float f; };
-    static const Cand all[] = {{256, 256, 1, 1.45f}, {256, 128, 1, 1.25f}, {128, 128, 2, 1.0f}, {128, 64, 3, 0.8f},
-                               {64, 64, 5, 0.55f}, {128, 32, 4, 0.35f}};
-    const int nk = (K + BK - 1) / BK;
-    Plan best = {128, 32, 1, nk};
-    float best_cost = 3.0e38f;
-    for (const Cand& c : all) {
-        const bool ok = N <= 32 ? c.bn == 32 : (N <= 64 ? c.bn == 64 : (c.bn != 32 && (c.bn <= 128 || N > 128)));
-        if (!ok) continue;
-        const long blocks = (long)((M + c.bm - 1) / c.bm) * ((N + c.bn - 1) / c.bn) * classes;
-        const long n = (blocks + NUM_CU - 1) / NUM_CU;
-        const long full = n / c.resident, rem = n % c.resident;
-        const float tile = (float)c.bm * c.bn / c.f;
-        float cost = (float)full * c.resident * tile;
-        if (rem) cost += (float)rem * tile / (rem == 1 && c.resident > 1 ? 0.62f : 0.9f);
-        if (cost < best_cost) {
-            best_cost = cost;
-            best = {c.bm, c.bn, 1, nk};
+// What the shared entry layer (conv_im2col_entry.h) needs to know about the bf16 kernels.
+struct Im2colBF16 {
+    typedef bf16 T;
+    static constexpr int BK = ::BK;
+    static constexpr int MIN_LOG_C = ::MIN_LOG_C;
+    static constexpr int CH_MASK = 7;
+    static constexpr bool HALF_STRIPS = true;       // the 128-row strip tile exists (strip_bm)
+    static constexpr int WGRAD_SLAB_ROWS = 64;
+    static constexpr int IMAGE_PX = 4;              // NHWC8 images: 4 pixels x 8 planes (2 groups of 4) per GEMM row
+    static constexpr int IMAGE_GROUPS = 2;          // groups of 4 planes the fold behind it handles: 32 / (4 * IMAGE_PX)
+    // Tile choice for the bf16 kernels: the fp32 planner's candidates plus the 8-wave 256-row tiles (one workgroup per CU,
+    // 128 KiB / 96 KiB of LDS).  At bf16 MFMA rates the 128x128 tile is bound by what a CU can pull out of L2 into LDS
+    // (32 KB per 64-deep slab) and by LDS read bandwidth (one ds_read_b128 per MFMA with 64x64 wave tiles); a 256x256 tile
+    // halves both per flop (128x64 wave tiles: 0.75 reads per MFMA), a 256x128 tile saves a quarter.  f: kernel_bench_bf16, r02.
+    static constexpr TileCand TILES[] = {{256, 256, 1, 1.45f}, {256, 128, 1, 1.25f}, {128, 128, 2, 1.0f}, {128, 64, 3, 0.8f},
+                                         {64, 64, 5, 0.55f}, {128, 32, 4, 0.35f}};
+    static constexpr int SPLIT_BELOW = NUM_CU / 2;
+
+    static int launch_gemm(const Gather& g, const bf16* w, size_t w_class_stride, int classes, Scatter o, const float* bias, int act,
+                           size_t dst_elems, void* ws, size_t ws_bytes, hipStream_t st) {
+        Plan p = im2col_plan<Im2colBF16>(g.M, o.N, g.K, classes);
+        bf16* final_dst = (bf16*)o.dst;
+        size_t part_stride = 0;
+        if (p.splits > 1) {
+            if (!ws || ws_bytes < gemm_ws_bytes(p, dst_elems)) {
+                p.splits = 1;   // not enough scratch: run un-split (slower, same result up to summation order)
+                p.kt_per_split = (g.K + BK - 1) / BK;
+            } else {
+                o.dst = ws;
+                part_stride = dst_elems;
+            }
         }
+        const bool f32out = p.splits > 1;
+        if (p.bm == 256 && p.bn == 256) launch_variant_h<256, 256, 2, 4, 4, 2>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
+        else if (p.bm == 256 && p.bn == 128) launch_variant_h<256, 128, 4, 2, 2, 2, 3>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
+        else if (p.bm == 128 && p.bn == 128) launch_variant_h<128, 128, 2, 2, 2, 2>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
+        else if (p.bm == 128 && p.bn == 64) launch_variant_h<128, 64, 2, 2, 2, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
+        else if (p.bm == 64 && p.bn == 64) launch_variant_h<64, 64, 2, 2, 1, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
+        else launch_variant_h<128, 32, 4, 1, 1, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
+        DWC_LAUNCH_CHECK();
+        if (p.splits > 1) return splitk_reduce((const float*)ws, final_dst, bias, dst_elems, p.splits, o.N, act, st);
+        return DWC_OK;
     }
-    const long blocks = (long)((M + best.bm - 1) / best.bm) * ((N + best.bn - 1) / best.bn) * classes;
-    if (blocks < NUM_CU / 2 && nk >= 8) {
-        int s = (int)((2 * NUM_CU + blocks - 1) / blocks);
-        if (s > nk / 4) s = nk / 4;
-        if (s > 32) s = 32;
-        if (s >= 2) {
-            best.kt_per_split = (nk + s - 1) / s;
-            best.splits = (nk + best.kt_per_split - 1) / best.kt_per_split;
-        }
+
+    // The ring strips of a data gradient (same_dgrad_geom / s2_ring_geom).  f32out: fp32 partial strips for fold_ring; otherwise
+    // whole-K strips rounded to bf16 at their place in the padded image.
+    template <bool F32OUT>
+    static void launch_strips_as(const StripSet& ss, int bm, dim3 grid, hipStream_t st) {
+        if (bm == 128) hipLaunchKernelGGL((gemm_strips_kernel_h<128, 64, 2, 2, 2, 1, F32OUT>), grid, dim3(256), 0, st, ss);
+        else hipLaunchKernelGGL((gemm_strips_kernel_h<64, 64, 2, 2, 1, 1, F32OUT>), grid, dim3(256), 0, st, ss);
     }
-    return best;
-}
-
-size_t gemm_ws_bytes_h(int M, int N, int K, int classes, size_t dst_elems) {
-    const Plan p = plan_gemm_h(M, N, K, classes);
-    return p.splits > 1 ? (size_t)p.splits * dst_elems * sizeof(float) : 0;
-}
-
-int launch_gemm_h(const Gather& g, const bf16* w, size_t w_class_stride, int classes, Scatter o, const float* bias, int act,
-                  size_t dst_elems, void* ws, size_t ws_bytes, hipStream_t st) {
-    Plan p = plan_gemm_h(g.M, o.N, g.K, classes);
-    bf16* final_dst = (bf16*)o.dst;
-    size_t part_stride = 0;
-    if (p.splits > 1) {
-        if (!ws || ws_bytes < (size_t)p.splits * dst_elems * sizeof(float)) {
-            p.splits = 1;
-            p.kt_per_split = (g.K + BK - 1) / BK;
-        } else {
-            o.dst = ws;
-            part_stride = dst_elems;
-        }
-    }
-    const bool f32out = p.splits > 1;
-    if (p.bm == 256 && p.bn == 256) launch_variant_h<256, 256, 2, 4, 4, 2>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
-    else if (p.bm == 256 && p.bn == 128) launch_variant_h<256, 128, 4, 2, 2, 2, 3>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
-    else if (p.bm == 128 && p.bn == 128) launch_variant_h<128, 128, 2, 2, 2, 2>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
-    else if (p.bm == 128 && p.bn == 64) launch_variant_h<128, 64, 2, 2, 2, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
-    else if (p.bm == 64 && p.bn == 64) launch_variant_h<64, 64, 2, 2, 1, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
-    else launch_variant_h<128, 32, 4, 1, 1, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, f32out, st);
-    DWC_LAUNCH_CHECK();
-    if (p.splits > 1) return splitk_reduce((const float*)ws, final_dst, bias, dst_elems, p.splits, o.N, act, st);
-    return DWC_OK;
-}
-
-// The ring strips of a data gradient (same_dgrad_geom / s2_ring_geom built with row tiles of bm = strip_bm(..., half = true)).
-// F32OUT: fp32 partial strips for fold_ring; otherwise whole-K strips rounded to bf16 at their place in the padded image.
-template <bool F32OUT>
-int launch_strips(const StripSet& ss, int bm, dim3 grid, hipStream_t st) {
-    if (bm == 128) hipLaunchKernelGGL((gemm_strips_kernel_h<128, 64, 2, 2, 2, 1, F32OUT>), grid, dim3(256), 0, st, ss);
-    else hipLaunchKernelGGL((gemm_strips_kernel_h<64, 64, 2, 2, 1, 1, F32OUT>), grid, dim3(256), 0, st, ss);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
-}
-
-int wgrad_launch_h(const FwdGeom& f, const bf16* dy, float* dw_oihw, int Cin, int Cout, int KHW, int cin_real, int cout_real,
-                   void* ws, size_t ws_bytes, hipStream_t st) {
-    const Gather& g = f.g;
-    if (Cout < 8) return DWC_EINVAL;
-    int splits, chunk;
-    wgrad_plan(g.M, g.K, Cout, &splits, &chunk, 1, 64);
-    if (!ws || ws_bytes < (size_t)splits * g.K * Cout * sizeof(float)) return DWC_EWORKSPACE;
-    float* slab = (float*)ws;
-    const int tk = (g.K + 127) / 128;
-#ifdef DWC_DEV_ABLATIONS      // timing-only ablations (WRONG results): compiled only by `make ABLATIONS=1`, never in the shipped .so
-    static const int dbg = getenv("DWC_WGRAD_DBG") ? atoi(getenv("DWC_WGRAD_DBG")) : 0;
-    if (Cout > 64 && dbg) {
-#define WG_DBG(D) case D: hipLaunchKernelGGL((wgrad_kernel_h<128, 2, 2, 2, 2, D>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk); break;
-        switch (dbg) { WG_DBG(1) WG_DBG(2) WG_DBG(3) WG_DBG(4) WG_DBG(7) default: return DWC_EINVAL; }
-#undef WG_DBG
-    } else
-#endif
-    if (Cout > 64) {
-        hipLaunchKernelGGL((wgrad_kernel_h<128, 2, 2, 2, 2>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy, Cout, slab,
-                           chunk);
-    } else if (Cout > 32) {
-        hipLaunchKernelGGL((wgrad_kernel_h<64, 2, 2, 2, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-    } else {
-        hipLaunchKernelGGL((wgrad_kernel_h<32, 4, 1, 1, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-    }
-    DWC_LAUNCH_CHECK();
-    wgrad_reduce(slab, dw_oihw, splits, g.K, Cout, Cin, KHW, cin_real, cout_real, st);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t dwc_bf16_weight_prepared_elems(int Cout, int Cin, int KH, int KW, int stride, int cout_pad, int cin_pad, int for_dgrad) {
-    return weight_prepared_elems(KH, KW, stride, cout_pad, cin_pad, for_dgrad, BK);
-}
-
-int dwc_bf16_weight_prepare_fwd(const float* w, void* out, int Cout, int Cin, int KH, int KW, int cout_pad, int cin_pad,
-                                void* stream) {
-    if (cout_pad < Cout || cin_pad < Cin) return DWC_EINVAL;
-    return weight_prepare_fwd(w, (bf16*)out, Cout, Cin, KH, KW, cout_pad, cin_pad, BK, (hipStream_t)stream);
-}
-
-int dwc_bf16_weight_prepare_dgrad(const float* w, void* out, int Cout, int Cin, int KH, int KW, int stride, int cout_pad,
-                                  int cin_pad, void* stream) {
-    if (cout_pad < Cout || cin_pad < Cin) return DWC_EINVAL;
-    if (stride == 2 && !(KH == 4 && KW == 4)) return DWC_EINVAL;
-    if (stride != 1 && stride != 2) return DWC_EINVAL;
-    return weight_prepare_dgrad(w, (bf16*)out, Cout, Cin, KH, KW, stride, cout_pad, cin_pad, BK, (hipStream_t)stream);
-}
-
-size_t dwc_bf16_conv2d_fwd_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
-    FwdGeom f;
-    if (!fwd_geom(nullptr, nullptr, B, H, W, Cin, Cout, KH, KW, stride, pad, &f, MIN_LOG_C)) return 0;
-    return gemm_ws_bytes_h(f.g.M, Cout, f.g.K, 1, f.dst_elems);
-}
-
-int dwc_bf16_conv2d_fwd(const void* x, const void* w_prepared, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
-                        int KH, int KW, int stride, int pad, int act, void* ws, size_t ws_bytes, void* stream) {
-    FwdGeom f;
-    if ((Cout & 7) || !fwd_geom(x, y, B, H, W, Cin, Cout, KH, KW, stride, pad, &f, MIN_LOG_C)) return DWC_EINVAL;
-    return launch_gemm_h(f.g, (const bf16*)w_prepared, 0, 1, f.o, bias, act, f.dst_elems, ws, ws_bytes, (hipStream_t)stream);
-}
-
-/* The frozen VGG16 trunk of the perceptual loss under bf16 (reference networks.py:639-688): zero-padded stride-1 convolution, forward
- * (the forward kernel with the zero rule: an out-of-image tap pushes its offset past the buffer descriptor and reads zeros) and
- * data gradient (the zero-padded correlation with the flipped filter; the adjoint of zero padding is a crop, no ring). */
-int dwc_bf16_conv2d_fwd_zeropad(const void* x, const void* w_prepared, const float* bias, void* y, int B, int H, int W, int Cin,
-                                int Cout, int KH, int KW, int stride, int pad, int act, void* ws, size_t ws_bytes, void* stream) {
-    FwdGeom f;
-    if ((Cout & 7) || !fwd_geom(x, y, B, H, W, Cin, Cout, KH, KW, stride, pad, &f, MIN_LOG_C)) return DWC_EINVAL;
-    f.g.reflect = 0;
-    return launch_gemm_h(f.g, (const bf16*)w_prepared, 0, 1, f.o, bias, act, f.dst_elems, ws, ws_bytes, (hipStream_t)stream);
-}
-
-size_t dwc_bf16_conv2d_bwd_data_zeropad_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int pad) {
-    FwdGeom f;
-    if ((Cin & 7) || (Cout & 7) || !zeropad_dgrad_geom(nullptr, nullptr, B, H, W, Cin, Cout, KH, KW, pad, &f)) return 0;
-    return gemm_ws_bytes_h(f.g.M, Cin, f.g.K, 1, f.dst_elems);
-}
-
-int dwc_bf16_conv2d_bwd_data_zeropad(const void* dy, const void* w_dgrad, void* dx, int B, int H, int W, int Cin, int Cout, int KH,
-                                     int KW, int pad, void* ws, size_t ws_bytes, void* stream) {
-    FwdGeom f;
-    if ((Cin & 7) || (Cout & 7) || !zeropad_dgrad_geom(dy, dx, B, H, W, Cin, Cout, KH, KW, pad, &f)) return DWC_EINVAL;
-    return launch_gemm_h(f.g, (const bf16*)w_dgrad, 0, 1, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, ws, ws_bytes, (hipStream_t)stream);
-}
-
-int dwc_bf16_conv2d_fwd_ex(const void* x, const void* w_prepared, const float* bias, void* y, int B, int H, int W, int Cin,
-                           int Cout, int KH, int KW, int stride_h, int stride_w, int pad_h, int pad_w, int act, void* stream) {
-    FwdGeom f;
-    if ((Cout & 7) || !fwd_geom_ex(x, y, B, H, W, Cin, Cout, KH, KW, stride_h, stride_w, pad_h, pad_w, &f, MIN_LOG_C)) return DWC_EINVAL;
-    return launch_gemm_h(f.g, (const bf16*)w_prepared, 0, 1, f.o, bias, act, f.dst_elems, nullptr, 0, (hipStream_t)stream);
-}
-
-size_t dwc_bf16_conv2d_bwd_data_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
-    BwdGeom f;
-    if (!bwd_geom(nullptr, nullptr, B, H, W, Cin, Cout, KH, KW, stride, pad, &f, BK, MIN_LOG_C)) return 0;
-    return gemm_ws_bytes_h(f.g.M, Cin, f.g.K, f.classes, f.dst_elems);
-}
-
-int dwc_bf16_conv2d_bwd_data(const void* dy, const void* w_dgrad, void* dxp, int B, int H, int W, int Cin, int Cout, int KH,
-                             int KW, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
-    BwdGeom f;
-    if ((Cin & 7) || !bwd_geom(dy, dxp, B, H, W, Cin, Cout, KH, KW, stride, pad, &f, BK, MIN_LOG_C)) return DWC_EINVAL;
-    return launch_gemm_h(f.g, (const bf16*)w_dgrad, f.wcs, f.classes, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, ws, ws_bytes,
-                         (hipStream_t)stream);
-}
-
-int dwc_bf16_reflect_pad_adjoint(const void* dxp, void* dx, int B, int H, int W, int C, int pad, void* stream);
-/* dwc_bf16_conv2d_bwd_data + dwc_bf16_reflect_pad_adjoint in one call: dx ([B,H,W,Cin]) = reflect-pad adjoint of the gradient of
- * the padded image.  Where the GEMM runs unsplit the interior of that image is written straight into dx and only its border ring
- * into dxp (scratch for [B,H+2pad,W+2pad,Cin] bf16), a band kernel then folds the ring onto dx: one pass over the tensor instead of
- * three.  Otherwise (split-K) the two-step form runs. */
-int dwc_bf16_conv2d_bwd_data_fold(const void* dy, const void* w_dgrad, void* dxp, void* dx, int B, int H, int W, int Cin, int Cout,
-                                  int KH, int KW, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
-    BwdGeom f;
-    if ((Cin & 7) || pad <= 0 || !bwd_geom(dy, dxp, B, H, W, Cin, Cout, KH, KW, stride, pad, &f, BK, MIN_LOG_C)) return DWC_EINVAL;
-    if (H < 2 * pad + 2 || W < 2 * pad + 2 || H > 65535 - 2 * pad || B > 65535) return DWC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const Plan p = plan_gemm_h(f.g.M, f.o.N, f.g.K, f.classes);
-    const bool direct = p.splits == 1;
-    if (direct) {
-        f.o.crop = pad; f.o.IH = H; f.o.IW = W; f.o.inner = dx;
-    }
-    int rc = launch_gemm_h(f.g, (const bf16*)w_dgrad, f.wcs, f.classes, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, ws, ws_bytes, st);
-    if (rc != DWC_OK) return rc;
-    if (!direct) return dwc_bf16_reflect_pad_adjoint(dxp, dx, B, H, W, Cin, pad, stream);
-    return fold_band((const bf16*)dxp, (bf16*)dx, B, H, W, Cin, pad, st);
-}
-
-/* bf16 twin of dwc_conv2d_bwd_data_s2_ring: ring of the padded gradient image of a 4x4 stride-2 reflect-pad-1 convolution as eight
- * strips into the bf16 scratch image dxp + band fold onto dx (interior by dwc_bf16_conv2d_s2_halo_bwd_data). */
-int dwc_bf16_conv2d_bwd_data_s2_ring(const void* dy, const void* w_dgrad, void* dxp, void* dx, int B, int H, int W, int Cin, int Cout,
-                                     void* stream) {
-    S2Ring f;
-    const int bm = strip_bm((long)B * max(W / 2 + 1, H / 2), (Cin + 63) / 64, 8, 1, true);
-    if (!dy || !w_dgrad || !dxp || !dx || (Cin & 7) || H > 65535 - 2 || B > 65535 ||
-        !s2_ring_geom(dy, w_dgrad, dxp, 2, B, H, W, Cin, Cout, &f, BK, MIN_LOG_C, bm))
-        return DWC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = launch_strips<false>(f.ss, bm, dim3(f.max_tiles, 1, 8), st);
-    if (rc != DWC_OK) return rc;
-    return fold_band((const bf16*)dxp, (bf16*)dx, B, H, W, Cin, 1, st);
-}
-
-/* dx (already holding the interior of the padded gradient image dxp) += the border ring of dxp folded back by the reflect rule:
- * the second half of dwc_bf16_conv2d_bwd_data_fold for producers with their own epilogue (dwc_bf16_conv2d_stem_crop). */
-int dwc_bf16_reflect_pad_adjoint_band(const void* dxp, void* dx, int B, int H, int W, int C, int pad, void* stream) {
-    if (B <= 0 || (C & 7) || pad <= 0 || H < 2 * pad + 2 || W < 2 * pad + 2 || H > 65535 || B > 65535) return DWC_EINVAL;
-    return fold_band((const bf16*)dxp, (bf16*)dx, B, H, W, C, pad, (hipStream_t)stream);
-}
-
-int dwc_bf16_reflect_pad_adjoint(const void* dxp, void* dx, int B, int H, int W, int C, int pad, void* stream) {
-    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || pad < 0 || pad >= H || pad >= W) return DWC_EINVAL;
-    if (!(C & 7) && H <= 65535 && B <= 65535) {
-        hipLaunchKernelGGL(fold_reflect_kernel_h8, dim3((W * (C / 8) + 255) / 256, H, B), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16*)dxp, (bf16*)dx, H, W, C / 8, pad, W + 2 * pad);
+    static int launch_strips(const StripSet& ss, int bm, dim3 grid, hipStream_t st, bool f32out) {
+        if (f32out) launch_strips_as<true>(ss, bm, grid, st);
+        else launch_strips_as<false>(ss, bm, grid, st);
         DWC_LAUNCH_CHECK();
         return DWC_OK;
     }
-    return fold_reflect((const bf16*)dxp, (bf16*)dx, B, H, W, C / 4, pad, W + 2 * pad, (hipStream_t)stream);
-}
 
-size_t dwc_bf16_conv2d_bwd_data_same_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int pad) {
-    SameDgrad f;
-    const int bm = strip_bm((long)B * pad * max(W + 2 * pad, H), (Cin + 63) / 64, 4, 1, true);
-    if (!same_dgrad_geom(nullptr, nullptr, nullptr, nullptr, nullptr, B, H, W, Cin, Cout, KH, KW, pad, &f, BK, bm)) return 0;
-    const size_t ring = (f.ring_total * f.parts * sizeof(float) + 255) / 256 * 256;
-    return ring + gemm_ws_bytes_h(f.g.M, Cin, f.g.K, 1, f.dst_elems);
-}
-
-static int same_dgrad_run_h(const void* dy, const void* w_dgrad, const void* w_dgrad_t, void* dx, int B, int H, int W, int Cin,
-                            int Cout, int KH, int KW, int pad, void* ws, size_t ws_bytes, void* stream, bool ring_only) {
-    SameDgrad f;
-    const int bm = strip_bm((long)B * pad * max(W + 2 * pad, H), (Cin + 63) / 64, 4, 1, true);
-    if ((Cin & 7) || !same_dgrad_geom(dy, w_dgrad, w_dgrad_t, dx, (float*)ws, B, H, W, Cin, Cout, KH, KW, pad, &f, BK, bm)) return DWC_EINVAL;
-    const size_t ring_bytes = (f.ring_total * f.parts * sizeof(float) + 255) / 256 * 256;
-    if (!ws || ws_bytes < ring_bytes) return DWC_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (!ring_only) {
-        int rc = launch_gemm_h(f.g, (const bf16*)w_dgrad, 0, 1, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, (char*)ws + ring_bytes,
-                               ws_bytes - ring_bytes, st);
-        if (rc != DWC_OK) return rc;
+    static int wgrad_launch(const FwdGeom& f, const bf16* dy, float* dw_oihw, int Cin, int Cout, int KHW, int cin_real, int cout_real,
+                            void* ws, size_t ws_bytes, hipStream_t st) {
+        const Gather& g = f.g;
+        if (Cout < 8) return DWC_EINVAL;
+        int splits, chunk;
+        if (!ws || ws_bytes < wgrad_ws_bytes(g.M, g.K, Cout, WGRAD_SLAB_ROWS, &splits, &chunk)) return DWC_EWORKSPACE;
+        float* slab = (float*)ws;
+        const int tk = (g.K + 127) / 128;
+#ifdef DWC_DEV_ABLATIONS      // timing-only ablations (WRONG results): compiled only by `make ABLATIONS=1`, never in the shipped .so
+        static const int dbg = getenv("DWC_WGRAD_DBG") ? atoi(getenv("DWC_WGRAD_DBG")) : 0;
+        if (Cout > 64 && dbg) {
+#define WG_DBG(D) case D: hipLaunchKernelGGL((wgrad_kernel_h<128, 2, 2, 2, 2, D>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk); break;
+            switch (dbg) { WG_DBG(1) WG_DBG(2) WG_DBG(3) WG_DBG(4) WG_DBG(7) default: return DWC_EINVAL; }
+#undef WG_DBG
+        } else
+#endif
+        if (Cout > 64) {
+            hipLaunchKernelGGL((wgrad_kernel_h<128, 2, 2, 2, 2>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy, Cout, slab,
+                               chunk);
+        } else if (Cout > 32) {
+            hipLaunchKernelGGL((wgrad_kernel_h<64, 2, 2, 2, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+        } else {
+            hipLaunchKernelGGL((wgrad_kernel_h<32, 4, 1, 1, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+        }
+        DWC_LAUNCH_CHECK();
+        wgrad_reduce(slab, dw_oihw, splits, g.K, Cout, Cin, KHW, cin_real, cout_real, st);
+        DWC_LAUNCH_CHECK();
+        return DWC_OK;
     }
-    const int rc = launch_strips<true>(f.ss, bm, dim3(f.max_tiles, f.parts, 4), st);
-    if (rc != DWC_OK) return rc;
-    return fold_ring((bf16*)dx, (const float*)ws, f, B, H, W, Cin, pad, st);
-}
 
-int dwc_bf16_conv2d_bwd_data_same(const void* dy, const void* w_dgrad, const void* w_dgrad_t, void* dx, int B, int H, int W,
-                                  int Cin, int Cout, int KH, int KW, int pad, void* ws, size_t ws_bytes, void* stream) {
-    return same_dgrad_run_h(dy, w_dgrad, w_dgrad_t, dx, B, H, W, Cin, Cout, KH, KW, pad, ws, ws_bytes, stream, false);
-}
+    // The 16-byte form where it takes the shape (bf16 only), otherwise the common 8-byte one.
+    static int fold_image(const bf16* dxp, bf16* dx, int B, int H, int W, int C, int pad, hipStream_t st) {
+        if (!(C & 7) && H <= 65535 && B <= 65535) {
+            hipLaunchKernelGGL(fold_reflect_kernel_h8, dim3((W * (C / 8) + 255) / 256, H, B), dim3(256), 0, st, dxp, dx, H, W, C / 8, pad,
+                               W + 2 * pad);
+            DWC_LAUNCH_CHECK();
+            return DWC_OK;
+        }
+        return fold_reflect(dxp, dx, B, H, W, C / 4, pad, W + 2 * pad, st);
+    }
 
-/* only the border ring: dx must already hold the interior (dwc_bf16_conv2d_same_halo with the zero rule and the dgrad weights) */
-int dwc_bf16_conv2d_bwd_data_ring(const void* dy, const void* w_dgrad, const void* w_dgrad_t, void* dx, int B, int H, int W,
-                                  int Cin, int Cout, int KH, int KW, int pad, void* ws, size_t ws_bytes, void* stream) {
-    return same_dgrad_run_h(dy, w_dgrad, w_dgrad_t, dx, B, H, W, Cin, Cout, KH, KW, pad, ws, ws_bytes, stream, true);
-}
+    // dwc_bf16_reflect_pad_adjoint_band: H, B <= 65535 are required here and not by the fp32 twin; the fp32 twin's checks for NULL
+    // tensors and C <= 0 are not made here.
+    static bool band_args_bad(const void* /*dxp*/, const void* /*dx*/, int B, int H, int /*C*/) { return H > 65535 || B > 65535; }
+};
 
-// gradient w.r.t. an NHWC8 image through a stem convolution: 4 pixels x 8 planes per GEMM row (see dwc_conv2d_bwd_data_image)
-size_t dwc_bf16_conv2d_bwd_data_image_ws_bytes(int B, int H, int W, int Cout, int KH, int KW, int pad) {
-    FwdGeom f;
-    if (!image_dgrad_geom(nullptr, nullptr, B, H, W, Cout, KH, KW, pad, &f, 4)) return 0;
-    return f.dst_elems * sizeof(bf16);
-}
+}  // namespace
 
-int dwc_bf16_conv2d_bwd_data_image(const void* dy, const void* w_wide, void* dx, int B, int H, int W, int Cout, int KH, int KW,
-                                   int pad, void* ws, size_t ws_bytes, void* stream) {
-    FwdGeom f;
-    if (!image_dgrad_geom(dy, ws, B, H, W, Cout, KH, KW, pad, &f, 4)) return DWC_EINVAL;
-    if (!ws || ws_bytes < f.dst_elems * sizeof(bf16)) return DWC_EWORKSPACE;
-    const int rc = launch_gemm_h(f.g, (const bf16*)w_wide, 0, 1, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, nullptr, 0,
-                                 (hipStream_t)stream);
-    if (rc != DWC_OK) return rc;
-    // (8 planes = 2 groups of 4 per pixel)
-    return fold_reflect((const bf16*)ws, (bf16*)dx, B, H, W, 2, pad, f.g.OW * 4, (hipStream_t)stream);
-}
+#define DWC_BF16_NAME(x) dwc_bf16_##x
+DWC_IM2COL_EXPORTS(DWC_BF16_NAME, Im2colBF16, void)
+#undef DWC_BF16_NAME
+
+extern "C" {
 
 /* the same gradient on conv_narrow_bf16.hip (patch staged once per block, taps dealt to the waves): w_frag = the wide bank in
  * fragment order (see dwc_bf16_conv2d_narrow); scratch as dwc_bf16_conv2d_bwd_data_image_ws_bytes */
@@ -965,39 +775,6 @@ int dwc_bf16_conv2d_bwd_data_image_narrow(const void* dy, const void* w_frag, vo
                                           DWC_ACT_NONE, 0, stream);
     if (rc != DWC_OK) return rc;
     return fold_reflect((const bf16*)ws, (bf16*)dx, B, H, W, 2, pad, f.g.OW * 4, (hipStream_t)stream);
-}
-
-size_t dwc_bf16_conv2d_bwd_weight_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    int splits, chunk;
-    wgrad_plan(B * Ho * Wo, KH * KW * Cin, Cout, &splits, &chunk, 1, 64);
-    return (size_t)splits * KH * KW * Cin * Cout * sizeof(float);
-}
-
-int dwc_bf16_conv2d_bwd_weight(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int KH,
-                               int KW, int stride, int pad, int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream) {
-    FwdGeom f;
-    if (!fwd_geom(x, nullptr, B, H, W, Cin, Cout, KH, KW, stride, pad, &f, MIN_LOG_C)) return DWC_EINVAL;
-    if (cin_real > Cin || cout_real > Cout || (Cout & 7)) return DWC_EINVAL;
-    return wgrad_launch_h(f, (const bf16*)dy, dw_oihw, Cin, Cout, KH * KW, cin_real, cout_real, ws, ws_bytes, (hipStream_t)stream);
-}
-
-size_t dwc_bf16_conv2d_bwd_weight_ex_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride_h, int stride_w,
-                                              int pad_h, int pad_w) {
-    FwdGeom f;
-    if (!fwd_geom_ex(nullptr, nullptr, B, H, W, Cin, Cout, KH, KW, stride_h, stride_w, pad_h, pad_w, &f, MIN_LOG_C)) return 0;
-    int splits, chunk;
-    wgrad_plan(f.g.M, f.g.K, Cout, &splits, &chunk, 1, 64);
-    return (size_t)splits * f.g.K * Cout * sizeof(float);
-}
-
-int dwc_bf16_conv2d_bwd_weight_ex(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int KH,
-                                  int KW, int stride_h, int stride_w, int pad_h, int pad_w, int cin_real, int cout_real, void* ws,
-                                  size_t ws_bytes, void* stream) {
-    FwdGeom f;
-    if (!fwd_geom_ex(x, nullptr, B, H, W, Cin, Cout, KH, KW, stride_h, stride_w, pad_h, pad_w, &f, MIN_LOG_C)) return DWC_EINVAL;
-    if (cin_real > Cin || cout_real > Cout || (Cout & 7)) return DWC_EINVAL;
-    return wgrad_launch_h(f, (const bf16*)dy, dw_oihw, Cin, Cout, KH * KW, cin_real, cout_real, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -142,42 +142,44 @@ struct Plan {
     int bm, bn, splits, kt_per_split;
 };
 
+// A candidate tile: `resident` workgroups of it fit on a CU, `f` = its measured MFMA rate at full residency relative to the 128x128 tile.
+struct TileCand { int bm, bn, resident; float f; };
+
 // Cost model (relative time of the busiest CU).  A CU holds up to `resident` workgroups of a
 // tile shape (LDS / VGPR limits of the direct-to-LDS kernel); it receives n = ceil(blocks/256)
 // of them and works through them `resident` at a time.  A full group runs at the tile's measured
-// MFMA-rate factor f (relative to 128x128 at 2 WG/CU, r01 kernel_bench: 130 / 108 / ~95 TFLOP/s);
+// MFMA-rate factor f (relative to 128x128 at 2 WG/CU);
 // a trailing partial group runs at reduced efficiency because fewer waves per SIMD are left to
 // cover barrier / LDS latency (one WG alone: 0.62).  This is what makes 768 tiles of 128x128
 // (1.5 groups) lose to 1536 tiles of 128x64 (exactly 2 groups) for the 3B-batched 3x3 convs.
-Plan plan_gemm(int M, int N, int K, int classes, int bk = 32) {
-    struct Cand { int bm, bn, resident; float f; };
-    static const Cand all[] = {{128, 128, 2, 1.0f}, {128, 64, 3, 0.85f}, {64, 64, 5, 0.72f}, {128, 32, 4, 0.5f}};
+// `bk`, `cands` and `split_below` belong to the caller's kernels (Im2colF32 / Im2colBF16).  A 32-column tile serves N <= 32 only, a
+// 64-column tile N <= 64 only, a tile wider than 128 columns needs N > 128.
+template <size_t NC>
+Plan plan_gemm(int M, int N, int K, int classes, int bk, const TileCand (&cands)[NC], int split_below) {
     const int nk = (K + bk - 1) / bk;
     Plan best = {128, 32, 1, nk};
     float best_cost = 3.0e38f;
-    auto valid = [N](const Cand& c) {
+    auto valid = [N](const TileCand& c) {
         if (N <= 32) return c.bn == 32;
         if (N <= 64) return c.bn == 64;
-        return c.bn != 32;
+        return c.bn != 32 && (c.bn <= 128 || N > 128);
     };
-    for (const Cand& c : all) {
+    for (const TileCand& c : cands) {
         if (!valid(c)) continue;
         const long blocks = (long)((M + c.bm - 1) / c.bm) * ((N + c.bn - 1) / c.bn) * classes;
         const long n = (blocks + NUM_CU - 1) / NUM_CU;
         const long full = n / c.resident, rem = n % c.resident;
         const float tile = (float)c.bm * c.bn / c.f;
         float cost = (float)full * c.resident * tile;
-        if (rem) cost += (float)rem * tile / (rem == 1 ? 0.62f : 0.9f);
+        if (rem) cost += (float)rem * tile / (rem == 1 && c.resident > 1 ? 0.62f : 0.9f);
         if (cost < best_cost) {
             best_cost = cost;
             best = {c.bm, c.bn, 1, nk};
         }
     }
-    // split-K: too few output tiles to fill the chip but a long contraction
+    // split-K: too few output tiles (fewer than `split_below`) to fill the chip but a long contraction
     const long blocks = (long)((M + best.bm - 1) / best.bm) * ((N + best.bn - 1) / best.bn) * classes;
-    // (r05: the threshold was NUM_CU / 2 -- 128 tiles of a 4096-deep contraction ran 128 slabs each, one barrier per slab: c1's
-    // discriminator tail launches 32.9 -> 28.5 us with up to 2 * NUM_CU tiles split, +28 reduce launches; net -0.2 ms per step)
-    if (blocks < 2 * NUM_CU && nk >= 8) {
+    if (blocks < split_below && nk >= 8) {
         int s = (int)((2 * NUM_CU + blocks - 1) / blocks);
         if (s > nk / 4) s = nk / 4;
         if (s > 32) s = 32;
@@ -189,8 +191,8 @@ Plan plan_gemm(int M, int N, int K, int classes, int bk = 32) {
     return best;
 }
 
-size_t gemm_ws_bytes(int M, int N, int K, int classes, size_t dst_elems, int bk = 32) {
-    const Plan p = plan_gemm(M, N, K, classes, bk);
+// scratch of a split plan: `splits` fp32 partial images of the destination (0: the plan runs unsplit)
+inline size_t gemm_ws_bytes(const Plan& p, size_t dst_elems) {
     return p.splits > 1 ? (size_t)p.splits * dst_elems * sizeof(float) : 0;
 }
 
@@ -230,6 +232,12 @@ void wgrad_plan(int M, int K, int N, int* splits, int* chunk, int classes = 1, i
     }
     *chunk = (int)best_c * slab_rows;
     *splits = (int)((slabs + best_c - 1) / best_c);
+}
+
+// wgrad_plan + the scratch its launch needs: one fp32 [K][N] slab per split
+inline size_t wgrad_ws_bytes(int M, int K, int N, int slab_rows, int* splits, int* chunk) {
+    wgrad_plan(M, K, N, splits, chunk, 1, slab_rows);
+    return (size_t)*splits * K * N * sizeof(float);
 }
 
 struct FwdGeom {
@@ -339,6 +347,16 @@ bool zeropad_dgrad_geom(const void* dy, void* dx, int B, int H, int W, int Cin, 
     return true;
 }
 
+// Row-tile height of the ring-strip launches (64-column tiles either way).  bf16: 128 rows per workgroup -- two 32x32 accumulators
+// per wave sharing every weight fragment -- once the strips hold enough rows to fill the chip with tiles of that size (measured,
+// benchmarks/ring_bench.py: -10..15 % at batch 128, equal at 384), 64 below that.  fp32 (split products): always 64 -- the
+// 128-row form has to halve its accumulator tile per MFMA group and lost 10..30 % at every batch.
+// `rows` = GEMM rows of the longest strip, `strips` x `tiles_n` x `parts` workgroups per row tile.
+inline int strip_bm(long rows, int tiles_n, int strips, int parts, bool half) {
+    if (!half) return 64;
+    return ((rows + 127) / 128) * tiles_n * strips * parts >= 2 * NUM_CU ? 128 : 64;
+}
+
 // Data gradient of a stride-1 "same" reflect-padded convolution (2*pad == K-1, square filter) WITHOUT building the whole
 // padded gradient image: the interior is a zero-padded correlation of dY with the flipped filter over the H x W grid
 // (power-of-two geometry, no wasted rows), written straight into dx; the border ring of the padded image -- the only
@@ -351,16 +369,18 @@ struct SameDgrad {
     StripSet ss;
     size_t ring_elems[4], ring_total, dst_elems;
     int max_tiles, parts;
+    int bm;                 // row tile of the strip launch (strip_bm)
 };
 
 bool same_dgrad_geom(const void* dy, const void* w_dg, const void* w_dg_t, void* dx, float* ring, int B, int H, int W,
-                     int Cin, int Cout, int KH, int KW, int pad, SameDgrad* f, int bk = 32, int bm = 64) {
+                     int Cin, int Cout, int KH, int KW, int pad, SameDgrad* f, int bk, bool half) {
     if (!conv_args_ok(B, H, W, Cout, Cin, KH, KW, 1, pad)) return false;
     if (Cout < bk || dwc_ilog2_exact(Cout) < 5 || (Cin & 3) || pad <= 0 || KH != KW || 2 * pad != KH - 1) return false;
     if (H < 2 * pad + 2 || W < 2 * pad + 2) return false;    // the two border bands of an axis must not overlap
     const int Wp = W + 2 * pad;
     const int magic = kw_magic_for(KW, KH * KW + 64);
     if (magic < 0) return false;
+    const int bm = f->bm = strip_bm((long)B * pad * max(W + 2 * pad, H), (Cin + 63) / 64, 4, 1, half);
     auto base = [&](Gather& g, int OH, int OW, int off_h, int off_w, int tap_t) {
         g.src = dy; g.SH = H; g.SW = W; g.SC = Cout; g.logSC = dwc_ilog2_exact(Cout);
         g.OH = OH; g.OW = OW; g.KH = KH; g.KW = KW; g.kw_magic = magic;
@@ -420,15 +440,17 @@ bool same_dgrad_geom(const void* dy, const void* w_dg, const void* w_dg_t, void*
 struct S2Ring {
     StripSet ss;
     int max_tiles;
+    int bm;                 // row tile of the strip launch (strip_bm)
 };
 
 inline bool s2_ring_geom(const void* dy, const void* w_dgrad, void* dxp, size_t elem_bytes, int B, int H, int W, int Cin, int Cout,
-                         S2Ring* f, int bk = 32, int min_log_c = 2, int bm = 64) {
+                         S2Ring* f, int bk, int min_log_c, bool half) {
     if (B <= 0 || H < 4 || W < 4 || (H & 1) || (W & 1) || (Cin & 3) || dwc_ilog2_exact(Cout) < min_log_c) return false;
     const int H2 = H / 2, W2 = W / 2, Hp = H + 2, Wp = W + 2;
     const int Kp = (4 * Cout + bk - 1) / bk * bk;
     const size_t wcs = (size_t)Cin * Kp;                   // elements per class matrix (bwd_geom)
     const int magic = kw_magic_for(2, 64);
+    const int bm = f->bm = strip_bm((long)B * max(W / 2 + 1, H / 2), (Cin + 63) / 64, 8, 1, half);
     f->max_tiles = 0;
     f->ss.kt_per_part = Kp / bk;
     f->ss.part_stride = 0;
@@ -463,16 +485,6 @@ inline bool s2_ring_geom(const void* dy, const void* w_dgrad, void* dxp, size_t 
         if (st.tiles > f->max_tiles) f->max_tiles = st.tiles;
     }
     return true;
-}
-
-// Row-tile height of the ring-strip launches (64-column tiles either way).  bf16: 128 rows per workgroup -- two 32x32 accumulators
-// per wave sharing every weight fragment -- once the strips hold enough rows to fill the chip with tiles of that size (measured,
-// benchmarks/ring_bench.py: -10..15 % at batch 128, equal at 384), 64 below that.  fp32 (split products): always 64 -- the
-// 128-row form has to halve its accumulator tile per MFMA group and lost 10..30 % at every batch.
-// `rows` = GEMM rows of the longest strip, `strips` x `tiles_n` x `parts` workgroups per row tile.
-inline int strip_bm(long rows, int tiles_n, int strips, int parts, bool half) {
-    if (!half) return 64;
-    return ((rows + 127) / 128) * tiles_n * strips * parts >= 2 * NUM_CU ? 128 : 64;
 }
 
 // Data gradient w.r.t. an NHWC4 IMAGE (stem convolutions, Cin = 4): N = 4 would fill 1/8 of a 32-wide MFMA tile, so

@@ -24,7 +24,7 @@
 
 #include <atomic>
 
-#include "conv_fold.h"
+#include "conv_im2col_entry.h"
 
 namespace {
 
@@ -631,75 +631,103 @@ static int x3_mode() {
 static bool wgrad_x3_on() { return (x3_mode() & 2) != 0; }
 static bool gemm_x3_on(int K) { return (x3_mode() & 1) != 0 && K >= 128; }
 
-int launch_gemm(const Gather& g, const float* w, size_t w_class_stride, int classes, Scatter o, const float* bias, int act,
-                size_t dst_elems, void* ws, size_t ws_bytes, hipStream_t st) {
-    Plan p = plan_gemm(g.M, o.N, g.K, classes);
-    float* final_dst = (float*)o.dst;
-    size_t part_stride = 0;
-    if (p.splits > 1) {
-        if (!ws || ws_bytes < (size_t)p.splits * dst_elems * sizeof(float)) {
-            p.splits = 1;   // not enough scratch: run un-split (slower, same result up to summation order)
-            p.kt_per_split = (g.K + BK - 1) / BK;
-        } else {
-            o.dst = (float*)ws;
-            part_stride = dst_elems;
+// What the shared entry layer (conv_im2col_entry.h) needs to know about the fp32 kernels.
+struct Im2colF32 {
+    typedef float T;
+    static constexpr int BK = ::BK;
+    static constexpr int MIN_LOG_C = 2;             // a 16-byte staging chunk is 4 channels
+    static constexpr int CH_MASK = 3;
+    static constexpr bool HALF_STRIPS = false;      // only the 64-row strip tile exists (strip_bm)
+    static constexpr int WGRAD_SLAB_ROWS = 32;
+    static constexpr int IMAGE_PX = 8;              // NHWC4 images: 8 pixels x 4 planes per GEMM row
+    static constexpr int IMAGE_GROUPS = 1;          // groups of 4 planes the fold behind it handles: 32 / (4 * IMAGE_PX)
+    // (f relative to 128x128 at 2 WG/CU: r01 kernel_bench, 130 / 108 / ~95 TFLOP/s)
+    static constexpr TileCand TILES[] = {{128, 128, 2, 1.0f}, {128, 64, 3, 0.85f}, {64, 64, 5, 0.72f}, {128, 32, 4, 0.5f}};
+    // (r05: the threshold was NUM_CU / 2 -- 128 tiles of a 4096-deep contraction ran 128 slabs each, one barrier per slab: c1's
+    // discriminator tail launches 32.9 -> 28.5 us with up to 2 * NUM_CU tiles split, +28 reduce launches; net -0.2 ms per step)
+    static constexpr int SPLIT_BELOW = 2 * NUM_CU;
+
+    static int launch_gemm(const Gather& g, const float* w, size_t w_class_stride, int classes, Scatter o, const float* bias, int act,
+                           size_t dst_elems, void* ws, size_t ws_bytes, hipStream_t st) {
+        Plan p = im2col_plan<Im2colF32>(g.M, o.N, g.K, classes);
+        float* final_dst = (float*)o.dst;
+        size_t part_stride = 0;
+        if (p.splits > 1) {
+            if (!ws || ws_bytes < gemm_ws_bytes(p, dst_elems)) {
+                p.splits = 1;   // not enough scratch: run un-split (slower, same result up to summation order)
+                p.kt_per_split = (g.K + BK - 1) / BK;
+            } else {
+                o.dst = (float*)ws;
+                part_stride = dst_elems;
+            }
         }
+        if (gemm_x3_on(g.K)) {
+            // (split accumulators need the registers of two tiles: the 128x128 plan runs as 128x64 with twice the column tiles)
+            if (p.bm == 128 && p.bn >= 64) launch_variant<128, 64, 2, 2, 2, 1, true>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
+            else if (p.bm == 64 && p.bn == 64) launch_variant<64, 64, 2, 2, 1, 1, true>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
+            else launch_variant<128, 32, 4, 1, 1, 1, true>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
+        } else if (p.bm == 128 && p.bn == 128) launch_variant<128, 128, 2, 2, 2, 2>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
+        else if (p.bm == 128 && p.bn == 64) launch_variant<128, 64, 2, 2, 2, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
+        else if (p.bm == 64 && p.bn == 64) launch_variant<64, 64, 2, 2, 1, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
+        else launch_variant<128, 32, 4, 1, 1, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
+        DWC_LAUNCH_CHECK();
+        if (p.splits > 1) return splitk_reduce((const float*)ws, final_dst, bias, dst_elems, p.splits, o.N, act, st);
+        return DWC_OK;
     }
-    if (gemm_x3_on(g.K)) {
-        // (split accumulators need the registers of two tiles: the 128x128 plan runs as 128x64 with twice the column tiles)
-        if (p.bm == 128 && p.bn >= 64) launch_variant<128, 64, 2, 2, 2, 1, true>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
-        else if (p.bm == 64 && p.bn == 64) launch_variant<64, 64, 2, 2, 1, 1, true>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
-        else launch_variant<128, 32, 4, 1, 1, 1, true>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
-    } else if (p.bm == 128 && p.bn == 128) launch_variant<128, 128, 2, 2, 2, 2>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
-    else if (p.bm == 128 && p.bn == 64) launch_variant<128, 64, 2, 2, 2, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
-    else if (p.bm == 64 && p.bn == 64) launch_variant<64, 64, 2, 2, 1, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
-    else launch_variant<128, 32, 4, 1, 1, 1>(g, w, w_class_stride, classes, o, bias, act, p, part_stride, st);
-    DWC_LAUNCH_CHECK();
-    if (p.splits > 1) return splitk_reduce((const float*)ws, final_dst, bias, dst_elems, p.splits, o.N, act, st);
-    return DWC_OK;
-}
 
-// The ring strips of a data gradient (same_dgrad_geom / s2_ring_geom built with row tiles of `bm`).  Only the 64-row tile exists
-// here: strip_bm(..., half = false) never asks for another.
-int launch_strips(const StripSet& ss, int bm, dim3 grid, hipStream_t st) {
-    if (bm != 64) return DWC_EINVAL;
-    if (gemm_x3_on(ss.s[0].g.K)) hipLaunchKernelGGL((conv_gemm_strips_kernel<64, 64, 2, 2, 1, 1, true>), grid, dim3(256), 0, st, ss);
-    else hipLaunchKernelGGL((conv_gemm_strips_kernel<64, 64, 2, 2, 1, 1>), grid, dim3(256), 0, st, ss);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
-}
+    // The ring strips of a data gradient (same_dgrad_geom / s2_ring_geom).  Only the 64-row tile exists here, and every
+    // destination is fp32: `f32out` makes no difference.
+    static int launch_strips(const StripSet& ss, int bm, dim3 grid, hipStream_t st, bool /*f32out*/) {
+        if (bm != 64) return DWC_EINVAL;
+        if (gemm_x3_on(ss.s[0].g.K)) hipLaunchKernelGGL((conv_gemm_strips_kernel<64, 64, 2, 2, 1, 1, true>), grid, dim3(256), 0, st, ss);
+        else hipLaunchKernelGGL((conv_gemm_strips_kernel<64, 64, 2, 2, 1, 1>), grid, dim3(256), 0, st, ss);
+        DWC_LAUNCH_CHECK();
+        return DWC_OK;
+    }
 
-int wgrad_launch(const FwdGeom& f, const float* dy, float* dw_oihw, int Cin, int Cout, int KHW, int cin_real, int cout_real,
-                 void* ws, size_t ws_bytes, hipStream_t st) {
-    const Gather& g = f.g;
-    int splits, chunk;
-    wgrad_plan(g.M, g.K, Cout, &splits, &chunk);
-    if (!ws || ws_bytes < (size_t)splits * g.K * Cout * sizeof(float)) return DWC_EWORKSPACE;
-    float* slab = (float*)ws;
-    const int tk = (g.K + 127) / 128;
-    if (wgrad_x3_on()) {
-        if (Cout > 64)
-            hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2, true>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
+    static int wgrad_launch(const FwdGeom& f, const float* dy, float* dw_oihw, int Cin, int Cout, int KHW, int cin_real, int cout_real,
+                            void* ws, size_t ws_bytes, hipStream_t st) {
+        const Gather& g = f.g;
+        int splits, chunk;
+        if (!ws || ws_bytes < wgrad_ws_bytes(g.M, g.K, Cout, WGRAD_SLAB_ROWS, &splits, &chunk)) return DWC_EWORKSPACE;
+        float* slab = (float*)ws;
+        const int tk = (g.K + 127) / 128;
+        if (wgrad_x3_on()) {
+            if (Cout > 64)
+                hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2, true>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
+                                   Cout, slab, chunk);
+            else if (Cout > 32)
+                hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+            else
+                hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+        } else if (Cout > 64) {
+            hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
                                Cout, slab, chunk);
-        else if (Cout > 32)
-            hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-        else
-            hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-    } else if (Cout > 64) {
-        hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
-                           Cout, slab, chunk);
-    } else if (Cout > 32) {
-        hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-    } else {
-        hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+        } else if (Cout > 32) {
+            hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+        } else {
+            hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+        }
+        DWC_LAUNCH_CHECK();
+        wgrad_reduce(slab, dw_oihw, splits, g.K, Cout, Cin, KHW, cin_real, cout_real, st);
+        DWC_LAUNCH_CHECK();
+        return DWC_OK;
     }
-    DWC_LAUNCH_CHECK();
-    wgrad_reduce(slab, dw_oihw, splits, g.K, Cout, Cin, KHW, cin_real, cout_real, st);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
-}
+
+    static int fold_image(const float* dxp, float* dx, int B, int H, int W, int C, int pad, hipStream_t st) {
+        return fold_reflect(dxp, dx, B, H, W, C / 4, pad, W + 2 * pad, st);
+    }
+
+    // dwc_reflect_pad_adjoint_band: NULL tensors and C <= 0 are rejected here and not by the bf16 twin; the bf16 twin's limits
+    // H, B <= 65535 are not applied here.
+    static bool band_args_bad(const void* dxp, const void* dx, int /*B*/, int /*H*/, int C) { return !dxp || !dx || C <= 0; }
+};
 
 }  // namespace
+
+#define DWC_F32_NAME(x) dwc_##x
+DWC_IM2COL_EXPORTS(DWC_F32_NAME, Im2colF32, float)
+#undef DWC_F32_NAME
 
 extern "C" {
 
@@ -713,228 +741,11 @@ int dwc_x3_gemm_mode(int mode) {
     return prev;
 }
 
-size_t dwc_weight_prepared_elems(int Cout, int Cin, int KH, int KW, int stride, int cout_pad, int cin_pad, int for_dgrad) {
-    return weight_prepared_elems(KH, KW, stride, cout_pad, cin_pad, for_dgrad, BK);
-}
-
-int dwc_weight_prepare_fwd(const float* w, float* out, int Cout, int Cin, int KH, int KW, int cout_pad, int cin_pad,
-                           void* stream) {
-    if (cout_pad < Cout || cin_pad < Cin) return DWC_EINVAL;
-    return weight_prepare_fwd(w, out, Cout, Cin, KH, KW, cout_pad, cin_pad, BK, (hipStream_t)stream);
-}
-
-int dwc_weight_prepare_dgrad(const float* w, float* out, int Cout, int Cin, int KH, int KW, int stride, int cout_pad,
-                             int cin_pad, void* stream) {
-    if (cout_pad < Cout || cin_pad < Cin) return DWC_EINVAL;
-    if (stride == 2 && !(KH == 4 && KW == 4)) return DWC_EINVAL;
-    if (stride != 1 && stride != 2) return DWC_EINVAL;
-    return weight_prepare_dgrad(w, out, Cout, Cin, KH, KW, stride, cout_pad, cin_pad, BK, (hipStream_t)stream);
-}
-
-size_t dwc_conv2d_fwd_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
-    FwdGeom f;
-    if (!fwd_geom(nullptr, nullptr, B, H, W, Cin, Cout, KH, KW, stride, pad, &f)) return 0;
-    return gemm_ws_bytes(f.g.M, Cout, f.g.K, 1, f.dst_elems);
-}
-
-int dwc_conv2d_fwd(const float* x, const float* w_hwio, const float* bias, float* y, int B, int H, int W, int Cin, int Cout,
-                   int KH, int KW, int stride, int pad, int act, void* ws, size_t ws_bytes, void* stream) {
-    FwdGeom f;
-    if (!fwd_geom(x, y, B, H, W, Cin, Cout, KH, KW, stride, pad, &f)) return DWC_EINVAL;
-    return launch_gemm(f.g, w_hwio, 0, 1, f.o, bias, act, f.dst_elems, ws, ws_bytes, (hipStream_t)stream);
-}
-
-// Zero-padded convolutions (the frozen VGG16 of the perceptual loss, reference networks.py:639-688: nn.Conv2d(padding=1)):
-// the forward kernel with the zero rule instead of the reflect rule, and as data gradient the zero-padded correlation
-// with the flipped filter on the H x W grid (the adjoint of zero padding is a crop: nothing to fold).
-int dwc_conv2d_fwd_zeropad(const float* x, const float* w_prepared, const float* bias, float* y, int B, int H, int W, int Cin,
-                           int Cout, int KH, int KW, int stride, int pad, int act, void* ws, size_t ws_bytes, void* stream) {
-    FwdGeom f;
-    if (!fwd_geom(x, y, B, H, W, Cin, Cout, KH, KW, stride, pad, &f)) return DWC_EINVAL;
-    f.g.reflect = 0;
-    return launch_gemm(f.g, w_prepared, 0, 1, f.o, bias, act, f.dst_elems, ws, ws_bytes, (hipStream_t)stream);
-}
-
-
-size_t dwc_conv2d_bwd_data_zeropad_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int pad) {
-    FwdGeom f;
-    if (!zeropad_dgrad_geom(nullptr, nullptr, B, H, W, Cin, Cout, KH, KW, pad, &f)) return 0;
-    return gemm_ws_bytes(f.g.M, Cin, f.g.K, 1, f.dst_elems);
-}
-
-int dwc_conv2d_bwd_data_zeropad(const float* dy, const float* w_dgrad, float* dx, int B, int H, int W, int Cin, int Cout, int KH,
-                                int KW, int pad, void* ws, size_t ws_bytes, void* stream) {
-    FwdGeom f;
-    if (!zeropad_dgrad_geom(dy, dx, B, H, W, Cin, Cout, KH, KW, pad, &f)) return DWC_EINVAL;
-    return launch_gemm(f.g, w_dgrad, 0, 1, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, ws, ws_bytes, (hipStream_t)stream);
-}
-
-// forward / weight gradient with per-axis stride and reflect pad (no scratch on the forward: never split)
-int dwc_conv2d_fwd_ex(const float* x, const float* w_prepared, const float* bias, float* y, int B, int H, int W, int Cin,
-                      int Cout, int KH, int KW, int stride_h, int stride_w, int pad_h, int pad_w, int act, void* stream) {
-    FwdGeom f;
-    if (!fwd_geom_ex(x, y, B, H, W, Cin, Cout, KH, KW, stride_h, stride_w, pad_h, pad_w, &f)) return DWC_EINVAL;
-    return launch_gemm(f.g, w_prepared, 0, 1, f.o, bias, act, f.dst_elems, nullptr, 0, (hipStream_t)stream);
-}
-
-size_t dwc_conv2d_bwd_weight_ex_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride_h, int stride_w,
-                                         int pad_h, int pad_w) {
-    FwdGeom f;
-    if (!fwd_geom_ex(nullptr, nullptr, B, H, W, Cin, Cout, KH, KW, stride_h, stride_w, pad_h, pad_w, &f)) return 0;
-    int splits, chunk;
-    wgrad_plan(f.g.M, f.g.K, Cout, &splits, &chunk);
-    return (size_t)splits * f.g.K * Cout * sizeof(float);
-}
-
-int dwc_conv2d_bwd_weight_ex(const float* x, const float* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int KH,
-                             int KW, int stride_h, int stride_w, int pad_h, int pad_w, int cin_real, int cout_real, void* ws,
-                             size_t ws_bytes, void* stream) {
-    FwdGeom f;
-    if (!fwd_geom_ex(x, nullptr, B, H, W, Cin, Cout, KH, KW, stride_h, stride_w, pad_h, pad_w, &f)) return DWC_EINVAL;
-    if (cin_real > Cin || cout_real > Cout) return DWC_EINVAL;
-    return wgrad_launch(f, dy, dw_oihw, Cin, Cout, KH * KW, cin_real, cout_real, ws, ws_bytes, (hipStream_t)stream);
-}
-
-size_t dwc_conv2d_bwd_data_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
-    BwdGeom f;
-    if (!bwd_geom(nullptr, nullptr, B, H, W, Cin, Cout, KH, KW, stride, pad, &f)) return 0;
-    return gemm_ws_bytes(f.g.M, Cin, f.g.K, f.classes, f.dst_elems);
-}
-
-int dwc_reflect_pad_adjoint(const float* dxp, float* dx, int B, int H, int W, int C, int pad, void* stream) {
-    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || pad < 0 || pad >= H || pad >= W) return DWC_EINVAL;
-    return fold_reflect(dxp, dx, B, H, W, C / 4, pad, W + 2 * pad, (hipStream_t)stream);
-}
-
-/* dx (already holding the interior of the padded gradient image dxp [B][H+2pad][W+2pad][C]) += the border ring of dxp folded back by
- * the reflect rule; only the band of dx a ring pixel folds onto is visited (fp32 twin of dwc_bf16_reflect_pad_adjoint_band). */
-int dwc_reflect_pad_adjoint_band(const float* dxp, float* dx, int B, int H, int W, int C, int pad, void* stream) {
-    if (!dxp || !dx || B <= 0 || C <= 0 || (C & 3) || pad <= 0 || H < 2 * pad + 2 || W < 2 * pad + 2) return DWC_EINVAL;
-    return fold_band(dxp, dx, B, H, W, C, pad, (hipStream_t)stream);
-}
-
-/* The same for a padded gradient image whose rows are `pitch` >= W + 2*pad pixels apart (the 8-pixel-group grid of
+/* dwc_reflect_pad_adjoint for a padded gradient image whose rows are `pitch` >= W + 2*pad pixels apart (the 8-pixel-group grid of
  * dwc_x3_conv2d_narrow's image gradient). */
 int dwc_reflect_pad_adjoint_pitch(const float* dxp, float* dx, int B, int H, int W, int C, int pad, int pitch, void* stream) {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || pad < 0 || pad >= H || pad >= W || pitch < W + 2 * pad) return DWC_EINVAL;
     return fold_reflect(dxp, dx, B, H, W, C / 4, pad, pitch, (hipStream_t)stream);
-}
-
-
-size_t dwc_conv2d_bwd_data_same_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int pad) {
-    SameDgrad f;
-    const int bm = strip_bm((long)B * pad * max(W + 2 * pad, H), (Cin + 63) / 64, 4, 1, false);
-    if (!same_dgrad_geom(nullptr, nullptr, nullptr, nullptr, nullptr, B, H, W, Cin, Cout, KH, KW, pad, &f, 32, bm)) return 0;
-    const size_t ring = (f.ring_total * f.parts * sizeof(float) + 255) / 256 * 256;
-    return ring + gemm_ws_bytes(f.g.M, Cin, f.g.K, 1, f.dst_elems);
-}
-
-static int same_dgrad_run(const float* dy, const float* w_dgrad, const float* w_dgrad_t, float* dx, int B, int H, int W, int Cin,
-                          int Cout, int KH, int KW, int pad, void* ws, size_t ws_bytes, void* stream, bool ring_only);
-
-int dwc_conv2d_bwd_data_same(const float* dy, const float* w_dgrad, const float* w_dgrad_t, float* dx, int B, int H, int W,
-                             int Cin, int Cout, int KH, int KW, int pad, void* ws, size_t ws_bytes, void* stream) {
-    return same_dgrad_run(dy, w_dgrad, w_dgrad_t, dx, B, H, W, Cin, Cout, KH, KW, pad, ws, ws_bytes, stream, false);
-}
-
-// Only the border ring: dx must already hold the interior (dwc_x3_ / dwc_h2_conv2d_same_add_ws with the zero rule).
-int dwc_conv2d_bwd_data_ring(const float* dy, const float* w_dgrad, const float* w_dgrad_t, float* dx, int B, int H, int W,
-                             int Cin, int Cout, int KH, int KW, int pad, void* ws, size_t ws_bytes, void* stream) {
-    return same_dgrad_run(dy, w_dgrad, w_dgrad_t, dx, B, H, W, Cin, Cout, KH, KW, pad, ws, ws_bytes, stream, true);
-}
-
-static int same_dgrad_run(const float* dy, const float* w_dgrad, const float* w_dgrad_t, float* dx, int B, int H, int W, int Cin,
-                          int Cout, int KH, int KW, int pad, void* ws, size_t ws_bytes, void* stream, bool ring_only) {
-    SameDgrad f;
-    const int bm = strip_bm((long)B * pad * max(W + 2 * pad, H), (Cin + 63) / 64, 4, 1, false);
-    if (!same_dgrad_geom(dy, w_dgrad, w_dgrad_t, dx, (float*)ws, B, H, W, Cin, Cout, KH, KW, pad, &f, 32, bm)) return DWC_EINVAL;
-    const size_t ring_bytes = (f.ring_total * f.parts * sizeof(float) + 255) / 256 * 256;
-    if (!ws || ws_bytes < ring_bytes) return DWC_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (!ring_only) {
-        int rc = launch_gemm(f.g, w_dgrad, 0, 1, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, (char*)ws + ring_bytes,
-                             ws_bytes - ring_bytes, st);
-        if (rc != DWC_OK) return rc;
-    }
-    const int rc = launch_strips(f.ss, bm, dim3(f.max_tiles, f.parts, 4), st);
-    if (rc != DWC_OK) return rc;
-    return fold_ring(dx, (const float*)ws, f, B, H, W, Cin, pad, st);
-}
-
-
-size_t dwc_conv2d_bwd_data_image_ws_bytes(int B, int H, int W, int Cout, int KH, int KW, int pad) {
-    FwdGeom f;
-    if (!image_dgrad_geom(nullptr, nullptr, B, H, W, Cout, KH, KW, pad, &f)) return 0;
-    return f.dst_elems * sizeof(float);
-}
-
-int dwc_conv2d_bwd_data_image(const float* dy, const float* w_wide, float* dx, int B, int H, int W, int Cout, int KH, int KW,
-                              int pad, void* ws, size_t ws_bytes, void* stream) {
-    FwdGeom f;
-    if (!image_dgrad_geom(dy, (float*)ws, B, H, W, Cout, KH, KW, pad, &f)) return DWC_EINVAL;
-    if (!ws || ws_bytes < f.dst_elems * sizeof(float)) return DWC_EWORKSPACE;
-    const int rc = launch_gemm(f.g, w_wide, 0, 1, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, nullptr, 0, (hipStream_t)stream);
-    if (rc != DWC_OK) return rc;
-    return fold_reflect((const float*)ws, dx, B, H, W, 1, pad, f.g.OW * 8, (hipStream_t)stream);
-}
-
-int dwc_conv2d_bwd_data(const float* dy, const float* w_dgrad, float* dxp, int B, int H, int W, int Cin, int Cout, int KH,
-                        int KW, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
-    BwdGeom f;
-    if (!bwd_geom(dy, dxp, B, H, W, Cin, Cout, KH, KW, stride, pad, &f)) return DWC_EINVAL;
-    return launch_gemm(f.g, w_dgrad, f.wcs, f.classes, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, ws, ws_bytes, (hipStream_t)stream);
-}
-
-/* dwc_conv2d_bwd_data + dwc_reflect_pad_adjoint as one call (see dwc_bf16_conv2d_bwd_data_fold): where the GEMM runs unsplit the
- * interior of the padded gradient image goes straight into dx, only its border ring through the scratch image dxp, folded back by a
- * band kernel. */
-int dwc_conv2d_bwd_data_fold(const float* dy, const float* w_dgrad, float* dxp, float* dx, int B, int H, int W, int Cin, int Cout, int KH,
-                             int KW, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
-    BwdGeom f;
-    if ((Cin & 3) || pad <= 0 || !bwd_geom(dy, dxp, B, H, W, Cin, Cout, KH, KW, stride, pad, &f)) return DWC_EINVAL;
-    if (H < 2 * pad + 2 || W < 2 * pad + 2 || H > 65535 - 2 * pad || B > 65535) return DWC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const Plan p = plan_gemm(f.g.M, f.o.N, f.g.K, f.classes);
-    const bool direct = p.splits == 1;
-    if (direct) {
-        f.o.crop = pad; f.o.IH = H; f.o.IW = W; f.o.inner = dx;
-    }
-    int rc = launch_gemm(f.g, w_dgrad, f.wcs, f.classes, f.o, nullptr, DWC_ACT_NONE, f.dst_elems, ws, ws_bytes, st);
-    if (rc != DWC_OK) return rc;
-    if (!direct) return dwc_reflect_pad_adjoint(dxp, dx, B, H, W, Cin, pad, stream);
-    return fold_band((const float*)dxp, dx, B, H, W, Cin, pad, st);
-}
-
-/* Border ring + fold of the data gradient of a 4x4 stride-2 reflect-pad-1 convolution whose INTERIOR (the H x W pixels of dx)
- * has been written by a halo-tiled kernel (dwc_x3_conv2d_s2_bwd_data): the ring of the padded gradient image is computed as
- * eight thin strips into the scratch image dxp ([B][H+2][W+2][Cin], only its ring is touched) and folded onto dx by the
- * reflect rule (fold_band_kernel).  w_dgrad: the stride-2 data-gradient layout of dwc_weight_prepare_dgrad. */
-int dwc_conv2d_bwd_data_s2_ring(const float* dy, const float* w_dgrad, float* dxp, float* dx, int B, int H, int W, int Cin, int Cout,
-                                void* stream) {
-    S2Ring f;
-    const int bm = strip_bm((long)B * max(W / 2 + 1, H / 2), (Cin + 63) / 64, 8, 1, false);
-    if (!dy || !w_dgrad || !dxp || !dx || H > 65535 - 2 || B > 65535 ||
-        !s2_ring_geom(dy, w_dgrad, dxp, sizeof(float), B, H, W, Cin, Cout, &f, 32, 2, bm))
-        return DWC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = launch_strips(f.ss, bm, dim3(f.max_tiles, 1, 8), st);
-    if (rc != DWC_OK) return rc;
-    return fold_band((const float*)dxp, dx, B, H, W, Cin, 1, st);
-}
-
-size_t dwc_conv2d_bwd_weight_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    int splits, chunk;
-    wgrad_plan(B * Ho * Wo, KH * KW * Cin, Cout, &splits, &chunk);
-    return (size_t)splits * KH * KW * Cin * Cout * sizeof(float);
-}
-
-int dwc_conv2d_bwd_weight(const float* x, const float* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int KH,
-                          int KW, int stride, int pad, int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream) {
-    FwdGeom f;
-    if (!fwd_geom(x, nullptr, B, H, W, Cin, Cout, KH, KW, stride, pad, &f)) return DWC_EINVAL;
-    if (cin_real > Cin || cout_real > Cout) return DWC_EINVAL;
-    return wgrad_launch(f, dy, dw_oihw, Cin, Cout, KH * KW, cin_real, cout_real, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"
