@@ -1158,7 +1158,482 @@ int layernorm_bwd_t(const T* dy, const T* x, const float* mean, const float* inv
 
 }  // namespace
 
+namespace {
+
+// ---------------------------------------------------------------------------------------
+// batch norm over S equal batch segments (nn.BatchNorm2d of Conv2dBlock(norm='bn'), reference networks.py:547)
+// ---------------------------------------------------------------------------------------
+// x is [S * Bs][HW][C]; segment s = samples s * Bs ... (s + 1) * Bs - 1 is normalised with its own batch statistics: what the s-th of S
+// consecutive calls of the module on Bs samples computes.  Statistics pass: in_stats_partial as it is (per-(n, c) pivot, one partial
+// per row chunk), the rows split by plan_rows(Bs, HW) -- by the SEGMENT's batch, so that a segment's partials, and with them its
+// statistics bit for bit, do not depend on how many segments ride in the launch.  bn_stats_final then combines chunks and samples and
+// steps the running buffers; the apply passes have in_apply's geometry with the statistics indexed by the sample's segment.
+
+// (count, mean, M2) of two disjoint sets -> their union (Chan et al.); an empty side changes nothing
+__device__ __forceinline__ void bn_merge(float& cnt, float& d, float& m2, float cb, float db, float m2b) {
+    if (cb == 0.f) return;
+    if (cnt == 0.f) {
+        cnt = cb, d = db, m2 = m2b;
+        return;
+    }
+    const float tot = cnt + cb, delta = db - d;
+    d += delta * (cb / tot);
+    m2 += m2b + delta * delta * (cnt * (cb / tot));
+    cnt = tot;
+}
+
+// grid ceil(C / 64), 1024 threads = 64 channels x 16 sample lanes.  Per segment: lane g folds samples g, g + 16, ... (each: its chunks
+// summed in chunk order, mean offset d_n = (pivot_n - pivot_0) + s1_n / HW and M2_n = s2_n - s1_n^2 / HW about its own pivot, merged in
+// sample order), the 16 lanes are merged in lane order by lane 0: M2 = sum M2_n + HW sum (m_n - m)^2 in a fixed order, every mean
+// kept as a small offset from the segment's first pixel.  Lane 0 then steps the running buffers of its channel through `order`.
+template <typename T>
+__global__ __launch_bounds__(1024) void bn_stats_final(const T* __restrict__ x, const float* __restrict__ part, float* __restrict__ mean,
+                                                       float* __restrict__ rstd, float* __restrict__ running_mean,
+                                                       float* __restrict__ running_var, int S, int Bs, int HW, int C, int chunks,
+                                                       size_t plane, float eps, float momentum, dwc_bn_order order) {
+    __shared__ float sm[3][16][64];
+    __shared__ float st[2][DWC_BN_MAX_SEGMENTS][64];       // mean and unbiased variance per segment (written and read by lane 0 only)
+    const int cl = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cl;
+    const float hw = (float)HW;
+    for (int s = 0; s < S; ++s) {
+        float cnt = 0.f, d = 0.f, m2 = 0.f, p0 = 0.f;
+        if (c < C) {
+            p0 = (float)x[(size_t)s * Bs * HW * C + c];
+            for (int i = g; i < Bs; i += 16) {
+                const size_t n = (size_t)s * Bs + i;
+                const float* p = part + n * chunks * C + c;
+                float a = 0.f, b = 0.f;
+                int k = 0;
+                for (; k + 4 <= chunks; k += 4) {              // (four pairs in flight, summed in chunk order)
+                    float va[4], vb[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        va[u] = p[(size_t)(k + u) * C];
+                        vb[u] = p[plane + (size_t)(k + u) * C];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) a += va[u], b += vb[u];
+                }
+                for (; k < chunks; ++k) {
+                    a += p[(size_t)k * C];
+                    b += p[plane + (size_t)k * C];
+                }
+                const float dn = ((float)x[n * HW * C + c] - p0) + a / hw;
+                bn_merge(cnt, d, m2, hw, dn, fmaxf(b - a * (a / hw), 0.f));
+            }
+        }
+        __syncthreads();                                       // lane 0 has read the previous segment's partials
+        sm[0][g][cl] = cnt;
+        sm[1][g][cl] = d;
+        sm[2][g][cl] = m2;
+        __syncthreads();
+        if (g == 0 && c < C) {
+            for (int k = 1; k < 16; ++k) bn_merge(cnt, d, m2, sm[0][k][cl], sm[1][k][cl], sm[2][k][cl]);
+            const float mu = p0 + d;
+            mean[(size_t)s * C + c] = mu;
+            rstd[(size_t)s * C + c] = 1.f / sqrtf(m2 / cnt + eps);
+            st[0][s][cl] = mu;
+            st[1][s][cl] = m2 / (cnt - 1.f);
+        }
+    }
+    if (g == 0 && c < C && running_mean) {
+        float rm = running_mean[c], rv = running_var[c];
+        for (int j = 0; j < order.n; ++j) {
+            const int s = order.idx[j];
+            rm = (1.f - momentum) * rm + momentum * st[0][s][cl];
+            rv = (1.f - momentum) * rv + momentum * st[1][s][cl];
+        }
+        running_mean[c] = rm;
+        running_var[c] = rv;
+    }
+}
+
+// eval mode: the statistics are the running buffers
+__global__ void bn_eval_stats(const float* __restrict__ running_mean, const float* __restrict__ running_var, float* __restrict__ mean,
+                              float* __restrict__ rstd, int C, float eps) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    mean[c] = running_mean[c];
+    rstd[c] = 1.f / sqrtf(running_var[c] + eps);
+}
+
+// y = act((x - mean[s, c]) * (rstd[s, c] * gamma[c]) + beta[c]); grid (row chunks, S * Bs), geometry of in_apply
+template <typename T>
+__global__ __launch_bounds__(256) void bn_apply(const T* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                const float* __restrict__ gamma, const float* __restrict__ beta, T* __restrict__ y,
+                                                int Bs, int HW, int C, int rows_per_chunk, int act, unsigned long long* amax = nullptr,
+                                                unsigned amax_ep = 0) {
+    constexpr int V = VecOf<T>::V;
+    const int cq = C / V;
+    const int groups = 256 / cq;
+    const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
+    // (threads past the last row group walk no rows below but still reach the publish barrier)
+    unsigned am = 0;
+    const int n = blockIdx.y;
+    const size_t s = (size_t)(n / Bs) * C + col * V;
+    const float slope = dwc_act_slope(act);
+    float mu[V], sc[V], sh[V];
+    ldf<V>(mean, s, mu);
+    ldf<V>(rstd, s, sc);
+    if (gamma) {
+        float ga[V];
+        ldf<V>(gamma, (size_t)col * V, ga);
+#pragma unroll
+        for (int k = 0; k < V; ++k) sc[k] *= ga[k];
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) sh[k] = 0.f;
+    if (beta) ldf<V>(beta, (size_t)col * V, sh);
+    const size_t base = (size_t)n * HW * cq + col;
+    const int r0 = blockIdx.x * rows_per_chunk;
+    const int r1 = rg < groups ? min(HW, r0 + rows_per_chunk) : r0;
+    auto one = [&](const float (&v)[V], float (&o)[V]) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) o[k] = dwc_act_simple((v[k] - mu[k]) * sc[k] + sh[k], slope);
+        if constexpr (std::is_same<T, float>::value) am = dwc_amax_fold<V>(am, o);
+    };
+    int r = r0 + rg;
+    for (; r + 3 * groups < r1; r += 4 * groups) {        // four rows in flight per thread
+        float v[4][V], o[4][V];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) ldv(x, base + (size_t)(r + u * groups) * cq, v[u]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            one(v[u], o[u]);
+            stv(y, base + (size_t)(r + u * groups) * cq, o[u]);
+        }
+    }
+    for (; r < r1; r += groups) {
+        float v0[V], o0[V];
+        ldv(x, base + (size_t)r * cq, v0);
+        one(v0, o0);
+        stv(y, base + (size_t)r * cq, o0);
+    }
+    if constexpr (std::is_same<T, float>::value) {
+        __shared__ unsigned s_am[4];
+        dwc_amax_block_publish(amax, amax_ep, am, s_am);
+    }
+}
+
+// g = dy * act'(pre): the forward's own expression and rounding for pre (bn_apply), so that an element within an ulp of zero gets the
+// slope its forward output got
+template <int V>
+__device__ __forceinline__ void bn_grad_terms(const float (&xv)[V], const float (&dv)[V], const float (&mu)[V], const float (&rs)[V],
+                                              const float (&sc)[V], const float (&be)[V], float slope, float (&g)[V], float (&xh)[V]) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        const float xc = xv[k] - mu[k];
+        xh[k] = xc * rs[k];
+        g[k] = (xc * sc[k] + be[k]) > 0.f ? dv[k] : slope * dv[k];
+    }
+}
+
+// part[(n * chunks + chunk) * C + c] = sum g, second plane = sum g * xhat; grid (chunks, S * Bs)
+template <typename T>
+__global__ __launch_bounds__(256) void bn_bwd_partial(const T* __restrict__ dy, const T* __restrict__ x, const float* __restrict__ mean,
+                                                      const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, float* __restrict__ part, int Bs, int HW, int C,
+                                                      int rows_per_chunk, size_t plane, int act) {
+    constexpr int V = VecOf<T>::V;
+    __shared__ float sm[2 * 256 * V];
+    const int cq = C / V;
+    const int groups = 256 / cq;
+    const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
+    const int n = blockIdx.y, chunk = blockIdx.x;
+    const size_t base = (size_t)n * HW * cq + col;
+    const size_t s = (size_t)(n / Bs) * C + col * V;
+    const float slope = dwc_act_slope(act);
+    float mu[V], rs[V], sc[V], be[V];
+    ldf<V>(mean, s, mu);
+    ldf<V>(rstd, s, rs);
+#pragma unroll
+    for (int k = 0; k < V; ++k) sc[k] = rs[k], be[k] = 0.f;
+    if (gamma) {
+        float ga[V];
+        ldf<V>(gamma, (size_t)col * V, ga);
+#pragma unroll
+        for (int k = 0; k < V; ++k) sc[k] *= ga[k];
+    }
+    if (beta) ldf<V>(beta, (size_t)col * V, be);
+    const int r0 = chunk * rows_per_chunk;
+    const int r1 = min(HW, r0 + rows_per_chunk);
+    float s1[V], s2[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) s1[k] = s2[k] = 0.f;
+    auto acc = [&](const float (&xv)[V], const float (&dv)[V]) {
+        float g[V], xh[V];
+        bn_grad_terms<V>(xv, dv, mu, rs, sc, be, slope, g, xh);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            s1[k] += g[k];
+            s2[k] += g[k] * xh[k];
+        }
+    };
+    if (rg < groups) {
+        int r = r0 + rg;
+        for (; r + groups < r1; r += 2 * groups) {
+            const size_t i0 = base + (size_t)r * cq, i1 = i0 + (size_t)groups * cq;
+            float x0[V], x1[V], d0[V], d1[V];
+            ldv(x, i0, x0);
+            ldv(x, i1, x1);
+            ldv(dy, i0, d0);
+            ldv(dy, i1, d1);
+            acc(x0, d0);
+            acc(x1, d1);
+        }
+        for (; r < r1; r += groups) {
+            float x0[V], d0[V];
+            ldv(x, base + (size_t)r * cq, x0);
+            ldv(dy, base + (size_t)r * cq, d0);
+            acc(x0, d0);
+        }
+    }
+    colsum_groups<V>(s1, s2, sm, groups, cq, col, rg);
+    if (rg == 0) {
+        const size_t o = ((size_t)n * gridDim.x + chunk) * C + col * V;
+        stf<V>(part, o, s1);
+        stf<V>(part + plane, o, s2);
+    }
+}
+
+// grid ceil(C / 64), 1024 threads = 64 channels x 16 lanes.  Per segment the Bs * chunks partials of a channel are contiguous in the
+// partial index: lane g takes items g, g + 16, ..., the lanes are added in lane order -> sums[s * C + c] (sum g) and
+// sums[S * C + s * C + c] (sum g xhat); dbeta / dgamma = those added over the segments in segment order.
+__global__ __launch_bounds__(1024) void bn_bwd_final(const float* __restrict__ part, float* __restrict__ sums, float* __restrict__ dgamma,
+                                                     float* __restrict__ dbeta, int S, int Bs, int C, int chunks, size_t plane) {
+    __shared__ float sm[2][16][64];
+    const int cl = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cl;
+    const int total = Bs * chunks;
+    float dg = 0.f, db = 0.f;
+    for (int s = 0; s < S; ++s) {
+        float a = 0.f, b = 0.f;
+        if (c < C) {
+            const float* p = part + (size_t)s * total * C + c;
+            int k = g;
+            for (; k + 3 * 16 < total; k += 4 * 16) {
+                float va[4], vb[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    va[u] = p[(size_t)(k + 16 * u) * C];
+                    vb[u] = p[plane + (size_t)(k + 16 * u) * C];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) a += va[u], b += vb[u];
+            }
+            for (; k < total; k += 16) {
+                a += p[(size_t)k * C];
+                b += p[plane + (size_t)k * C];
+            }
+        }
+        __syncthreads();                                       // lane 0 has read the previous segment's partials
+        sm[0][g][cl] = a;
+        sm[1][g][cl] = b;
+        __syncthreads();
+        if (g == 0 && c < C) {
+            for (int k = 1; k < 16; ++k) {
+                a += sm[0][k][cl];
+                b += sm[1][k][cl];
+            }
+            sums[(size_t)s * C + c] = a;
+            sums[(size_t)(S + s) * C + c] = b;
+            db += a;
+            dg += b;
+        }
+    }
+    if (g == 0 && c < C) {
+        if (dgamma) dgamma[c] = dg;
+        if (dbeta) dbeta[c] = db;
+    }
+}
+
+// dx = gamma * rstd * (g - sum g / N - xhat * sum g xhat / N), the sums of the element's segment (coupled == 0, eval mode: the
+// statistics are constants, dx = gamma * rstd * g); grid (row chunks, S * Bs)
+template <typename T>
+__global__ __launch_bounds__(256) void bn_bwd_apply(const T* __restrict__ dy, const T* __restrict__ x, const float* __restrict__ mean,
+                                                    const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                    const float* __restrict__ beta, const float* __restrict__ sums, T* __restrict__ dx,
+                                                    int S, int Bs, int HW, int C, int rows_per_chunk, int act, int coupled,
+                                                    unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
+    constexpr int V = VecOf<T>::V;
+    const int cq = C / V;
+    const int groups = 256 / cq;
+    const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
+    // (threads past the last row group walk no rows below but still reach the publish barrier)
+    unsigned am = 0;
+    const int n = blockIdx.y;
+    const size_t s = (size_t)(n / Bs) * C + col * V;
+    const float slope = dwc_act_slope(act);
+    const float inv_n = 1.f / ((float)Bs * (float)HW);
+    float mu[V], rs[V], sc[V], be[V], k1[V], k2[V];
+    ldf<V>(mean, s, mu);
+    ldf<V>(rstd, s, rs);
+#pragma unroll
+    for (int k = 0; k < V; ++k) sc[k] = rs[k], be[k] = 0.f, k1[k] = k2[k] = 0.f;
+    if (gamma) {
+        float ga[V];
+        ldf<V>(gamma, (size_t)col * V, ga);
+#pragma unroll
+        for (int k = 0; k < V; ++k) sc[k] *= ga[k];
+    }
+    if (beta) ldf<V>(beta, (size_t)col * V, be);
+    if (coupled) {
+        ldf<V>(sums, s, k1);
+        ldf<V>(sums + (size_t)S * C, s, k2);
+#pragma unroll
+        for (int k = 0; k < V; ++k) k1[k] *= inv_n, k2[k] *= inv_n;
+    }
+    const size_t base = (size_t)n * HW * cq + col;
+    const int r0 = blockIdx.x * rows_per_chunk;
+    const int r1 = rg < groups ? min(HW, r0 + rows_per_chunk) : r0;
+    auto one = [&](const float (&xv)[V], const float (&dv)[V], float (&o)[V]) {
+        float g[V], xh[V];
+        bn_grad_terms<V>(xv, dv, mu, rs, sc, be, slope, g, xh);
+#pragma unroll
+        for (int k = 0; k < V; ++k) o[k] = sc[k] * (g[k] - k1[k] - xh[k] * k2[k]);
+        if constexpr (std::is_same<T, float>::value) am = dwc_amax_fold<V>(am, o);
+    };
+    int r = r0 + rg;
+    for (; r + 3 * groups < r1; r += 4 * groups) {        // four rows of x and dy in flight per thread
+        float xv[4][V], dv[4][V], o[4][V];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            ldv(x, base + (size_t)(r + u * groups) * cq, xv[u]);
+            ldv(dy, base + (size_t)(r + u * groups) * cq, dv[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            one(xv[u], dv[u], o[u]);
+            stv(dx, base + (size_t)(r + u * groups) * cq, o[u]);
+        }
+    }
+    for (; r < r1; r += groups) {
+        const size_t i0 = base + (size_t)r * cq;
+        float x0[V], d0[V], o0[V];
+        ldv(x, i0, x0);
+        ldv(dy, i0, d0);
+        one(x0, d0, o0);
+        stv(dx, i0, o0);
+    }
+    if constexpr (std::is_same<T, float>::value) {
+        __shared__ unsigned s_am[4];
+        dwc_amax_block_publish(amax, amax_ep, am, s_am);
+    }
+}
+
+// C a multiple of V with at most 256 column groups (any such C: a row group past the last whole one idles), 1..8 segments, a grid
+// the y dimension holds
+bool bn_shape_ok(int S, int Bs, int HW, int C, int V) {
+    return S >= 1 && S <= DWC_BN_MAX_SEGMENTS && Bs > 0 && HW > 0 && C >= V && C % V == 0 && C / V <= 256 && (long)S * Bs <= 65535;
+}
+
+size_t batchnorm_ws_bytes(int S, int Bs, int HW, int C) {      // two planes of partials + two planes of per-(segment, channel) sums
+    if (S < 1 || Bs < 1 || HW < 1 || C < 1) return 0;
+    const RowSplit rs = plan_rows(Bs, HW);
+    return ((size_t)2 * S * Bs * rs.chunks * C + (size_t)2 * S * C + 16) * sizeof(float);
+}
+
+template <typename T>
+int batchnorm_fwd_t(const T* x, const float* gamma, const float* beta, float* running_mean, float* running_var, T* y, float* mean,
+                    float* rstd, int S, int Bs, int HW, int C, float eps, float momentum, int act, int training, dwc_bn_order order,
+                    void* ws, size_t ws_bytes, void* stream, unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
+    if (!bn_shape_ok(S, Bs, HW, C, VecOf<T>::V) || !dwc_act_is_simple_host(act) || act < 0) return DWC_EINVAL;
+    if (order.n < 0 || order.n > DWC_BN_MAX_SEGMENTS || (!running_mean) != (!running_var)) return DWC_EINVAL;
+    for (int j = 0; j < order.n; ++j)
+        if (order.idx[j] < 0 || order.idx[j] >= S) return DWC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = S * Bs;
+    if (training) {
+        if ((long)Bs * HW < 2) return DWC_EINVAL;
+        if (!ws || ws_bytes < batchnorm_ws_bytes(S, Bs, HW, C)) return DWC_EWORKSPACE;
+        const RowSplit rs = plan_rows(Bs, HW);
+        const size_t plane = (size_t)B * rs.chunks * C;
+        float* part = (float*)ws;
+        hipLaunchKernelGGL(in_stats_partial<T>, dim3(rs.chunks, B), dim3(256), 0, st, x, part, HW, C, rs.rows_per_chunk, plane);
+        DWC_LAUNCH_CHECK();
+        hipLaunchKernelGGL(bn_stats_final<T>, dim3((C + 63) / 64), dim3(1024), 0, st, x, part, mean, rstd, running_mean, running_var, S,
+                           Bs, HW, C, rs.chunks, plane, eps, momentum, order);
+        DWC_LAUNCH_CHECK();
+    } else {
+        if (S != 1 || !running_mean) return DWC_EINVAL;
+        hipLaunchKernelGGL(bn_eval_stats, dim3((C + 255) / 256), dim3(256), 0, st, running_mean, running_var, mean, rstd, C, eps);
+        DWC_LAUNCH_CHECK();
+    }
+    const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
+    hipLaunchKernelGGL(bn_apply<T>, dim3(ra.chunks, B), dim3(256), 0, st, x, mean, rstd, gamma, beta, y, Bs, HW, C, ra.rows_per_chunk,
+                       act, amax, amax_ep);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+
+template <typename T>
+int batchnorm_bwd_t(const T* dy, const T* x, const float* mean, const float* rstd, const float* gamma, const float* beta, T* dx,
+                    float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act, int training, void* ws, size_t ws_bytes,
+                    void* stream, unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
+    if (!bn_shape_ok(S, Bs, HW, C, VecOf<T>::V) || !dwc_act_is_simple_host(act) || act < 0) return DWC_EINVAL;
+    if (training ? (long)Bs * HW < 2 : S != 1) return DWC_EINVAL;
+    if (!ws || ws_bytes < batchnorm_ws_bytes(S, Bs, HW, C)) return DWC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = S * Bs;
+    const RowSplit rs = plan_rows(Bs, HW);
+    const size_t plane = (size_t)B * rs.chunks * C;
+    float* part = (float*)ws;
+    float* sums = part + 2 * plane;
+    hipLaunchKernelGGL(bn_bwd_partial<T>, dim3(rs.chunks, B), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, part, Bs, HW, C,
+                       rs.rows_per_chunk, plane, act);
+    DWC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_bwd_final, dim3((C + 63) / 64), dim3(1024), 0, st, part, sums, dgamma, dbeta, S, Bs, C, rs.chunks, plane);
+    DWC_LAUNCH_CHECK();
+    const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
+    hipLaunchKernelGGL(bn_bwd_apply<T>, dim3(ra.chunks, B), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, sums, dx, S, Bs, HW, C,
+                       ra.rows_per_chunk, act, training ? 1 : 0, amax, amax_ep);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+
+}  // namespace
+
 extern "C" {
+
+size_t dwc_batchnorm_ws_bytes(int S, int Bs, int HW, int C) { return batchnorm_ws_bytes(S, Bs, HW, C); }
+
+int dwc_batchnorm_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, float* y,
+                      float* mean, float* rstd, int S, int Bs, int HW, int C, float eps, float momentum, int act, int training,
+                      dwc_bn_order order, void* ws, size_t ws_bytes, void* stream) {
+    return batchnorm_fwd_t<float>(x, gamma, beta, running_mean, running_var, y, mean, rstd, S, Bs, HW, C, eps, momentum, act, training,
+                                  order, ws, ws_bytes, stream);
+}
+int dwc_batchnorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                      float* dx, float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act, int training, void* ws,
+                      size_t ws_bytes, void* stream) {
+    return batchnorm_bwd_t<float>(dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, S, Bs, HW, C, act, training, ws, ws_bytes, stream);
+}
+/* ... raising the absmax slot of y / dx from the apply pass (see dwc_instnorm_fwd_amax below) */
+int dwc_batchnorm_fwd_amax(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, float* y,
+                           float* mean, float* rstd, int S, int Bs, int HW, int C, float eps, float momentum, int act, int training,
+                           dwc_bn_order order, void* ws, size_t ws_bytes, void* out_amax, unsigned out_epoch, void* stream) {
+    return batchnorm_fwd_t<float>(x, gamma, beta, running_mean, running_var, y, mean, rstd, S, Bs, HW, C, eps, momentum, act, training,
+                                  order, ws, ws_bytes, stream, (unsigned long long*)out_amax, out_epoch);
+}
+int dwc_batchnorm_bwd_amax(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                           const float* beta, float* dx, float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act,
+                           int training, void* ws, size_t ws_bytes, void* out_amax, unsigned out_epoch, void* stream) {
+    return batchnorm_bwd_t<float>(dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, S, Bs, HW, C, act, training, ws, ws_bytes, stream,
+                                  (unsigned long long*)out_amax, out_epoch);
+}
+int dwc_bf16_batchnorm_fwd(const void* x, const float* gamma, const float* beta, float* running_mean, float* running_var, void* y,
+                           float* mean, float* rstd, int S, int Bs, int HW, int C, float eps, float momentum, int act, int training,
+                           dwc_bn_order order, void* ws, size_t ws_bytes, void* stream) {
+    return batchnorm_fwd_t<dwc_bf16>((const dwc_bf16*)x, gamma, beta, running_mean, running_var, (dwc_bf16*)y, mean, rstd, S, Bs, HW, C,
+                                     eps, momentum, act, training, order, ws, ws_bytes, stream);
+}
+int dwc_bf16_batchnorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
+                           const float* beta, void* dx, float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act,
+                           int training, void* ws, size_t ws_bytes, void* stream) {
+    return batchnorm_bwd_t<dwc_bf16>((const dwc_bf16*)dy, (const dwc_bf16*)x, mean, rstd, gamma, beta, (dwc_bf16*)dx, dgamma, dbeta, S,
+                                     Bs, HW, C, act, training, ws, ws_bytes, stream);
+}
 
 size_t dwc_instnorm_ws_bytes(int B, int HW, int C) { return instnorm_ws_bytes(B, HW, C); }
 size_t dwc_layernorm_ws_bytes(int B, int HW, int C) { return layernorm_ws_bytes(B, HW, C); }

@@ -22,6 +22,13 @@ class AdvSpec(ctypes.Structure):               # struct dwc_adv_spec (passed by 
     _fields_ = [("target", c_f * 4), ("w_src", c_f * 4), ("w_cls", c_f * 4)]
 
 
+BN_MAX_SEGMENTS = 8                            # DWC_BN_MAX_SEGMENTS
+
+
+class BnOrder(ctypes.Structure):               # struct dwc_bn_order (passed by value)
+    _fields_ = [("n", c_int), ("idx", c_int * BN_MAX_SEGMENTS)]
+
+
 # name -> (restype, argtypes): mirrors include/dwcgan_hip.h one to one
 SIGNATURES = {
     "dwc_version": (c_int, []),
@@ -203,9 +210,17 @@ SIGNATURES = {
     "dwc_grad_penalty_fwd": (c_int, [c_fp] * 4 + [c_int] * 5 + [c_fp]),
     "dwc_grad_penalty_scale": (c_int, [c_fp] * 4 + [c_int] * 4 + [c_fp]),
     "dwc_src_head_seed": (c_int, [c_fp] * 3 + [c_int] * 3 + [c_fp]),
+    # ---- batch norm over S equal batch segments (hipdwc.batchnorm) ----
+    "dwc_batchnorm_ws_bytes": (c_sz, [c_int] * 4),
+    "dwc_batchnorm_fwd": (c_int, [c_fp] * 8 + [c_int] * 4 + [c_f, c_f, c_int, c_int, BnOrder, c_fp, c_sz, c_fp]),
+    "dwc_batchnorm_bwd": (c_int, [c_fp] * 9 + [c_int] * 6 + [c_fp, c_sz, c_fp]),
+    "dwc_batchnorm_fwd_amax": (c_int, [c_fp] * 8 + [c_int] * 4 + [c_f, c_f, c_int, c_int, BnOrder, c_fp, c_sz, c_fp, c_u, c_fp]),
+    "dwc_batchnorm_bwd_amax": (c_int, [c_fp] * 9 + [c_int] * 6 + [c_fp, c_sz, c_fp, c_u, c_fp]),
+    "dwc_bf16_batchnorm_fwd": (c_int, [c_fp] * 8 + [c_int] * 4 + [c_f, c_f, c_int, c_int, BnOrder, c_fp, c_sz, c_fp]),
+    "dwc_bf16_batchnorm_bwd": (c_int, [c_fp] * 9 + [c_int] * 6 + [c_fp, c_sz, c_fp]),
 }
 
-ABI_VERSION = 9                # DWC_ABI_VERSION of include/dwcgan_hip.h
+ABI_VERSION = 10               # DWC_ABI_VERSION of include/dwcgan_hip.h
 EINVAL = -1
 _ERRORS = {-1: "DWC_EINVAL (unsupported shape/argument)", -2: "DWC_EWORKSPACE (scratch too small)",
            -3: "DWC_ELAUNCH (kernel launch failed)"}

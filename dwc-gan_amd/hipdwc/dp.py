@@ -1,9 +1,12 @@
 """Data-parallel training over the GPUs of one node: one process per GPU, RCCL over xGMI.
 
 The reference is single-device; this is the new capability.  Every
-sample is independent through the conv/norm stack (IN/AdaIN per (n,c), LayerNorm per n, no
-BatchNorm) and every loss is a batch mean, so equal shards + gradient AVERAGING reproduce the
-global-batch gradient.  There is exactly one exchange per optimiser step: an all-reduce of
+sample is independent through the conv/norm stack of the shipped configurations (IN/AdaIN per
+(n,c), LayerNorm per n) and every loss is a batch mean, so equal shards + gradient AVERAGING
+reproduce the global-batch gradient.  The exception is ``dis.norm: bn`` (hipdwc.batchnorm): batch
+statistics and running buffers are PER RANK -- there is no SyncBN, the reference being
+single-device -- so an N-rank run normalises each shard with its own statistics and the ranks'
+running buffers drift apart (``warn_per_rank_batchnorm`` says so once).  There is exactly one exchange per optimiser step: an all-reduce of
 that optimiser's gradients (D: 13.99 M floats = 55.9 MB, G: 20.36 M = 81.4 MB at 128x128),
 packed into flat fp32 buckets so that RCCL sees a few large messages (xGMI is point-to-point:
 per-link bandwidth, not message rate, is the limit).
@@ -27,6 +30,18 @@ import torch.distributed as dist
 # all-reduce could only start when D's whole backward was done -- the overlap the reducer is built for needs several).  A ring all-reduce
 # over the 7 xGMI links of a GPU moves a 20 MB message in ~0.3 ms: still bandwidth-, not latency-bound.
 BUCKET_BYTES = 20 << 20
+_BN_WARNED = False
+
+
+def warn_per_rank_batchnorm(bn_layers, group=None):
+    """One warning per process when a network with batch-norm layers goes data parallel over more than one rank (module docstring)."""
+    global _BN_WARNED
+    if _BN_WARNED or not bn_layers or dist.get_world_size(group) <= 1:
+        return
+    _BN_WARNED = True
+    import warnings
+    warnings.warn("dis.norm 'bn' under data parallel: batch statistics and running buffers are per rank (no SyncBN); %d layers"
+                  % len(bn_layers))
 
 
 class GradAllReduce:

@@ -16,7 +16,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from hipdwc import ops, spectral
+from hipdwc import batchnorm, ops, spectral
 
 _CONV_ACTS = ("relu", "lrelu", "tanh", "sigmoid", "none")
 
@@ -71,6 +71,23 @@ class _PlainInstanceNorm(nn.InstanceNorm2d):
         return ops.instance_norm(x, None, None, residual=residual, relu=relu, eps=self.eps, token=token)
 
 
+class SegmentedBatchNorm2d(nn.BatchNorm2d):
+    """nn.BatchNorm2d (reference networks.py:547: same parameters, buffers and state_dict keys; construction draws nothing) whose
+    forward is hipdwc.batchnorm: ``segments`` = S equal parts of the batch, part s normalised with its own batch statistics -- the
+    s-th of S consecutive calls of the reference's module -- and the running buffers stepped once per entry of ``stat_order``
+    (default 0 .. S-1), in that sequence; ``num_batches_tracked`` counts those steps.  ``act``: none / relu / lrelu(0.1) fused into the
+    apply pass.  (The class name keeps ``weights_init`` away from it, as from nn.BatchNorm2d.)"""
+
+    def forward(self, x, act="none", segments=None, stat_order=None):
+        S = int(segments or 1)
+        order = tuple(range(S)) if stat_order is None else tuple(stat_order)
+        training = self.training or not self.track_running_stats
+        if self.training and self.track_running_stats and order:
+            self.num_batches_tracked.add_(len(order))
+        return batchnorm.batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, segments=S, order=order, act=act,
+                                    training=training, momentum=self.momentum, eps=self.eps)
+
+
 # --------------------------------------------------------------------------------------
 # basic blocks
 # --------------------------------------------------------------------------------------
@@ -107,9 +124,11 @@ class Conv2dBlock(nn.Module):
     What the shipped configurations use -- reflect padding, norm in {none, in, ln, adain}, activation in {relu, lrelu, tanh, sigmoid,
     none} -- is all HIP: the padding rule inside the convolution's gather, bias / activation in its epilogue, ReLU and the residual
     add in the norm's apply pass.  The rest of the reference's signature is reachable too (r05), through stock PyTorch-ROCm DEVICE
-    ops around the HIP convolution: ``pad_type`` zero / replicate at stride 1 (``F.pad``, then the convolution without padding), ``norm='bn'``
-    (``nn.BatchNorm2d``), ``activation`` prelu / selu (``nn.PReLU`` / ``F.selu``), and any norm followed by an activation other than
-    ReLU (the norm unfused, then the activation).  ``norm='sn'`` wraps the convolution in SpectralNorm like the reference: one power
+    ops around the HIP convolution: ``pad_type`` zero / replicate at stride 1 (``F.pad``, then the convolution without padding),
+    ``activation`` prelu / selu (``nn.PReLU`` / ``F.selu``), and any norm followed by an activation other than
+    ReLU (the norm unfused, then the activation).  ``norm='bn'`` is SegmentedBatchNorm2d on the HIP kernels with none / relu / lrelu
+    fused (``segments`` / ``stat_order``: the batch is S equal segments, each with its own batch statistics, the running buffers
+    stepped in ``stat_order``; hipdwc.batchnorm).  ``norm='sn'`` wraps the convolution in SpectralNorm like the reference: one power
     iteration per call (``segments`` = S: the batch is S equal segments and segment s uses the s-th of S consecutive iterations), the
     convolution on W_bar and 1 / sigma in a segmented epilogue (hipdwc.spectral)."""
 
@@ -135,7 +154,7 @@ class Conv2dBlock(nn.Module):
         elif norm == "adain":
             self.norm = AdaptiveInstanceNorm2d(output_dim)
         elif norm == "bn":
-            self.norm = nn.BatchNorm2d(output_dim)
+            self.norm = SegmentedBatchNorm2d(output_dim)
         elif norm == "none":
             self.norm = None
         elif norm == "sn":
@@ -155,11 +174,12 @@ class Conv2dBlock(nn.Module):
             return torch.nn.functional.selu(y)
         return {"lrelu": lambda t: torch.nn.functional.leaky_relu(t, 0.1), "tanh": torch.tanh, "sigmoid": torch.sigmoid}[self.act_kind](y)
 
-    def forward(self, x, residual=None, conv_token=None, res_token=None, sn=None, segments=None):
+    def forward(self, x, residual=None, conv_token=None, res_token=None, sn=None, segments=None, stat_order=None):
         """``conv_token`` / ``res_token`` (hipdwc.ops.ResGradToken, both optional): this block's convolution opens / this block's
         norm closes a residual block whose identity-branch gradient is added in the convolution's data-gradient epilogue.
         norm='sn' only: ``sn`` = a hipdwc.spectral.SNRun that already holds this block's iterations (MsImageDis runs one for all its
-        SN layers), else ``segments`` (default 1) iterations are run here."""
+        SN layers), else ``segments`` (default 1) iterations are run here.
+        norm='bn' only: ``segments`` / ``stat_order`` go to SegmentedBatchNorm2d.forward."""
         if x.shape[1] < 4:
             x = ops.pack_image(x)
         pad = self.padding
@@ -179,10 +199,23 @@ class Conv2dBlock(nn.Module):
             if not fused_act:
                 y = self._torch_act(y)
             return y if residual is None else y + residual
-        if self.norm_kind == "bn" or self.act_kind not in ("relu", "none"):
-            # off the shipped configurations: the norm on its own (HIP for in / ln / adain, torch for bn), then the activation
+        if self.norm_kind == "bn":
+            # training mode: the batch mean is subtracted per channel, d/d bias == 0 (as IN / AdaIN below); eval mode normalises with
+            # constants and the bias gradient is real
+            bias = self.conv.bias
+            train = self.norm.training or not self.norm.track_running_stats
+            if not train and getattr(bias, "_dwc_zero_grad", False):
+                bias._dwc_zero_grad = False
+            y = ops.conv2d(x, self.conv.weight, bias, self.stride, pad, "none", bias_grad=not train, token=conv_token)
+            fused = self.act_kind in batchnorm.ACTS
+            y = self.norm(y, act=self.act_kind if fused else "none", segments=segments, stat_order=stat_order)
+            if not fused:
+                y = self._torch_act(y)
+            return y if residual is None else y + residual
+        if self.act_kind not in ("relu", "none"):
+            # off the shipped configurations: the norm on its own, then the activation
             y = ops.conv2d(x, self.conv.weight, self.conv.bias, self.stride, pad, "none", token=conv_token)
-            y = self.norm(y) if self.norm_kind in ("bn", "ln") else self.norm(y, relu=False)
+            y = self.norm(y) if self.norm_kind == "ln" else self.norm(y, relu=False)
             y = torch.relu(y) if self.act_kind == "relu" else (y if self.act_kind == "none" else self._torch_act(y))
             return y if residual is None else y + residual
         y = ops.conv2d(x, self.conv.weight, self.conv.bias, self.stride, pad, "none",
@@ -392,17 +425,28 @@ class MsImageDis(nn.Module):
         n = self.num_scales if num_scales is None else num_scales
         return [blk.conv.module for s in range(n) for blk in self.cnns_feat[s] if blk.norm_kind == "sn"]
 
-    def forward(self, x, use_multiscales=True, segments=None):
-        """``segments`` = S (dis.norm 'sn' only): x is S equal segments and segment s sees the weights of the s-th of S consecutive
-        reference calls -- each call of the reference runs one power iteration per SN layer (networks.py:775-785), so S calls on
-        the S segments equal this one pass.  None: one call, one iteration, as in the reference.  Without SN layers the segments
-        change nothing."""
+    def bn_layers(self, num_scales=None):
+        """The batch-norm modules of the first ``num_scales`` scales (all by default), in module order."""
+        n = self.num_scales if num_scales is None else num_scales
+        return [blk.norm for s in range(n) for blk in self.cnns_feat[s] if blk.norm_kind == "bn"]
+
+    def forward(self, x, use_multiscales=True, segments=None, stat_order=None):
+        """``segments`` = S (dis.norm 'sn' / 'bn'): x is S equal segments that behave like S consecutive reference calls.  'sn': segment
+        s sees the weights of the s-th call -- each call of the reference runs one power iteration per SN layer (networks.py:775-785).
+        'bn': segment s is normalised with its own batch statistics and the running buffers are stepped once per entry of
+        ``stat_order`` (segment indices, default 0 .. S-1), in sequence -- each call of the reference normalises its own batch and
+        steps the buffers once (the 2x2 mean between the scales works per sample and keeps the segment layout).  None: one call, as in
+        the reference.  With any other norm the segments change nothing."""
         x = ops.pack_image(x)
         outputs = []
         layers = self.sn_layers(self.num_scales if use_multiscales else 1)
         sn = spectral.sn_power_iteration(layers, segments or 1) if layers else None
         for s in range(self.num_scales):
-            if sn is None:
+            if self.norm == "bn":
+                h = x
+                for blk in self.cnns_feat[s]:
+                    h = blk(h, segments=segments, stat_order=stat_order) if blk.norm_kind == "bn" else blk(h)
+            elif sn is None:
                 h = self.cnns_feat[s](x)
             else:
                 h = x
@@ -478,8 +522,8 @@ class MsImageDis(nn.Module):
 
     @staticmethod
     def split_outputs(outputs, sizes):
-        """Outputs of ONE forward over a concatenated batch -> per-segment output lists (the
-        discriminator has no cross-sample op, so this equals separate forwards)."""
+        """Outputs of ONE forward over a concatenated batch -> per-segment output lists.  Without a normalisation the discriminator has
+        no cross-sample op, so this equals separate forwards; with 'sn' / 'bn' it does when the forward was told the segments."""
         parts = [[] for _ in sizes]
         for src, cls in outputs:
             for p, s, c in zip(parts, torch.split(src, sizes), torch.split(cls, sizes)):

@@ -113,6 +113,7 @@ class Solver(nn.Module):
         self._reducers = {"dis": dp.OverlappedGradReducer(self.dis_opt.param_groups[0]["params"], group, bucket_bytes),
                           "gen": dp.OverlappedGradReducer(self.gen_opt.param_groups[0]["params"], group, bucket_bytes)}
         self.grad_sync = None
+        dp.warn_per_rank_batchnorm(self.dis.bn_layers(), group)
         # the persistent LSTM launches need ALL their workgroups resident while RCCL's all-reduce kernels (launched from inside
         # backward on a side stream) hold CUs of their own: keep those launches to half of a 256-CU device; larger grids take the
         # per-step kernels (dwc_lstm_seq_* return DWC_EINVAL above the cap)
@@ -281,6 +282,12 @@ class Solver(nn.Module):
             # iteration, so the two x_real passes see different weights -- ONE pass over the four segments, segment s at iteration s
             outs = self.dis(torch.cat([fakes[:B], x4, fakes[B:], x4]), segments=4)
             targets, w_src, w_cls, pairs = (0.0, 1.0, 0.0, 1.0), (gw,) * 4, (0.0, cw, 0.0, cw), ((0, 1), (2, 3))
+        elif self.dis.bn_layers():
+            # batch norm: each of those four calls normalises with its own batch statistics and steps the running buffers once.  The
+            # two x_real calls are identical in VALUE (training-mode statistics do not read the buffers), so x_real rides once with
+            # doubled weights as below; only the buffers see it twice, in the reference's sequence fake, real, fake1, real.
+            outs = self.dis(torch.cat([fakes, x4]), segments=3, stat_order=(0, 2, 1, 2))
+            targets, w_src, w_cls, pairs = (0.0, 0.0, 1.0), (gw, gw, 2.0 * gw), (0.0, 0.0, 2.0 * cw), ((0, 2), (1, 2))
         else:
             # ONE discriminator pass over [x_fake, x_fake1, x_real]; D(x_real) enters both loss terms as
             # in the reference (which evaluates it twice, with identical values)
@@ -372,8 +379,9 @@ class Solver(nn.Module):
             self.loss_gen_recon_s_rand = self.criterion_l1(style_rand, style1)
             self.loss_gen_cycrecon_x = ops.l1_mean(x_cycle, x4, image=True) if cyc else 0
 
-            # one pass over [x_fake, x_fake1] (spectral norm: the reference's two calls, one iteration each)
-            outs = self.dis(x_all[B:], segments=2 if self.dis.sn_layers() else None)
+            # one pass over [x_fake, x_fake1] (spectral norm: the reference's two calls, one iteration each; batch norm: each call's own
+            # batch statistics, the running buffers stepped twice)
+            outs = self.dis(x_all[B:], segments=2 if self.dis.sn_layers() or self.dis.bn_layers() else None)
             if self.dis.gan_type == "lsgan" and self.dis.dataset in ("CelebA", "CUB200"):
                 self.loss_gen_adv = self.dis.adv_loss(outs, B, label_trg, targets=(1.0, 1.0), w_src=(cfg["gan_w"],) * 2,
                                                       w_cls=(cfg["cls_w"],) * 2)

@@ -48,7 +48,7 @@ extern "C" {
 /* Version of this C ABI: bumped with every change of an entry point's signature or of a structure passed through it (r05: 5 --
  * dwc_weight_refresh_multi gained has_h2 / epoch, the dwc_h2_* / dwc_*_amax entry points).  A binding must refuse a library that
  * reports another number: symbols alone do not tell a changed argument list (hipdwc/_lib.py does). */
-#define DWC_ABI_VERSION 9
+#define DWC_ABI_VERSION 10
 int dwc_version(void);
 /* The fp32 im2col kernels (dwc_conv2d_fwd / _bwd_data* / _bwd_weight*, ring strips) take their inner products as exact three-way
  * bf16 split products on the bf16 matrix cores by default (r04; fp32 operands, results and accumulation -- see
@@ -706,6 +706,49 @@ int dwc_grad_penalty_scale(const float* g, const float* k, const float* dout, fl
 /* d[r][c] = w_s[c] * act'(a[r][c]) (act in {none, relu, lrelu}, the derivative read off the activation OUTPUT a): the gradient of
  * the sum of the 1x1 'src' head's map w.r.t. the pre-activation of the layer below it, in one pass.  C a multiple of 4. */
 int dwc_src_head_seed(const float* a, const float* w_s, float* d, int rows, int C, int act, void* stream);
+
+/* ---- batch normalisation over S equal batch segments (ABI 10; reference networks.py:547 nn.BatchNorm2d inside Conv2dBlock;
+ *      csrc/norm.hip) ---------------------------------------------------------------------------------------------
+ * x, y, dy, dx: [S * Bs][HW][C] NHWC, fp32 or bf16; segment s = samples s * Bs ... (s + 1) * Bs - 1 behaves like the s-th of S
+ * consecutive calls of the module on Bs samples: N = Bs * HW values per (segment, channel).  Statistics, gamma / beta [C] (NULL: 1 / 0)
+ * and their gradients are fp32.
+ *   training != 0:  mean / rstd [S * C] are OUTPUTS of the forward (rstd = 1 / sqrt(biased variance + eps)), kept for the backward.
+ *                   Per-sample mean and M2 about the sample's first pixel, combined over the chunks and the Bs samples with the
+ *                   parallel-variance formula in a fixed order (no atomics, no E[x^2] - E[x]^2: bit-identical run to run, and the
+ *                   statistics of a segment do not depend on S).  running_mean / running_var [C] (both NULL: not tracked) are
+ *                   updated IN PLACE, per channel in sequence: for j < order.n, r = (1 - momentum) r + momentum * stat[order.idx[j]]
+ *                   with the unbiased variance M2 / (N - 1).  `order` travels by value in the kernel arguments.
+ *   training == 0:  S = 1; mean = running_mean, rstd = 1 / sqrt(running_var + eps), nothing is written to the running buffers; the
+ *                   backward drops the two coupling terms.
+ *   y = act((x - mean[s,c]) * rstd[s,c] * gamma[c] + beta[c]), act in {DWC_ACT_NONE, DWC_ACT_RELU, DWC_ACT_LRELU}.
+ *   _bwd: g = dy * act'(pre) with pre recomputed from x;  dgamma[c] = sum g * xhat, dbeta[c] = sum g over ALL segments (NULL: skipped);
+ *         dx = gamma * rstd * (g - sum_s g / N - xhat * sum_s g xhat / N) with the sums of the element's own segment.
+ * DWC_EINVAL: C not a multiple of 4 (fp32) / 8 (bf16) or more than 256 such groups, S outside 1..8, order.n > 8, an order entry
+ * >= S, N < 2 in training, S * Bs > 65535.  Scratch: dwc_batchnorm_ws_bytes.  The _amax forms (fp32) raise the absmax slot of y / dx. */
+#define DWC_BN_MAX_SEGMENTS 8
+typedef struct dwc_bn_order {
+    int n;                          /* number of running-statistics updates, 0..8 */
+    int idx[DWC_BN_MAX_SEGMENTS];   /* segment whose statistics the j-th update takes */
+} dwc_bn_order;
+size_t dwc_batchnorm_ws_bytes(int S, int Bs, int HW, int C);
+int dwc_batchnorm_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, float* y,
+                      float* mean, float* rstd, int S, int Bs, int HW, int C, float eps, float momentum, int act, int training,
+                      dwc_bn_order order, void* ws, size_t ws_bytes, void* stream);
+int dwc_batchnorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                      float* dx, float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act, int training, void* ws,
+                      size_t ws_bytes, void* stream);
+int dwc_batchnorm_fwd_amax(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, float* y,
+                           float* mean, float* rstd, int S, int Bs, int HW, int C, float eps, float momentum, int act, int training,
+                           dwc_bn_order order, void* ws, size_t ws_bytes, void* out_amax, unsigned out_epoch, void* stream);
+int dwc_batchnorm_bwd_amax(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                           const float* beta, float* dx, float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act,
+                           int training, void* ws, size_t ws_bytes, void* out_amax, unsigned out_epoch, void* stream);
+int dwc_bf16_batchnorm_fwd(const void* x, const float* gamma, const float* beta, float* running_mean, float* running_var, void* y,
+                           float* mean, float* rstd, int S, int Bs, int HW, int C, float eps, float momentum, int act, int training,
+                           dwc_bn_order order, void* ws, size_t ws_bytes, void* stream);
+int dwc_bf16_batchnorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
+                           const float* beta, void* dx, float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act,
+                           int training, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
