@@ -1,4 +1,4 @@
-// nn.Linear (+ ReLU) on activations of a few dozen to a few hundred rows: the style -> AdaIN-parameter MLP (reference
+// nn.Linear (+ ReLU / LeakyReLU 0.1) on activations of a few dozen to a few hundred rows: the style -> AdaIN-parameter MLP (reference
 // networks.py:491-503, LinearBlock :587-634) and the style encoder's mapping (networks_v2.py:116-121), forward and backward.
 //
 // Rounds 1-5 ran these as 1x1 convolutions on the im2col GEMM: 16..384 rows against 64..4096 columns and a 64..256-deep contraction --
@@ -20,6 +20,9 @@ __device__ __forceinline__ f32x4v lin_mfma(float a, float b, f32x4v c) { return 
 
 constexpr int LIN_MAX_WAVES = 16;   // waves of one workgroup = slices of the contraction of ONE output tile
 constexpr int LIN_GROUP = 8;        // 16-deep steps whose operands are requested together (one memory round trip per group)
+
+// dy * act'(y) read off the saved OUTPUT (dwc_act_grad's rule); ReLU keeps its exact zero
+__device__ __forceinline__ float lin_act_grad(float y, float g, float slope) { return y > 0.f ? g : (slope == 0.f ? 0.f : slope * g); }
 
 // The launches are latency-bound, not bandwidth- or FLOP-bound (a first version with one wave walking the whole contraction behind a
 // one-deep prefetch measured SLOWER than the im2col GEMM it replaced: 256 dependent round trips for the 4096-deep data gradient).  So:
@@ -65,7 +68,7 @@ __device__ __forceinline__ f32x4v lin_contract(int steps, LoadA load_a, LoadB lo
 // y[M][N] = act(x[M][K] . w[N][K]^T + bias[N]).  K % 16 == 0, N % 16 == 0.  Both operands: one 16-byte load per lane and step.
 __global__ __launch_bounds__(64 * LIN_MAX_WAVES) void linear_small_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                               const float* __restrict__ bias, float* __restrict__ y, int M,
-                                                                              int N, int K, int relu, int tiles_n) {
+                                                                              int N, int K, int act, float slope, int tiles_n) {
     __shared__ float red[LIN_MAX_WAVES * 256];
     const int tn = blockIdx.x % tiles_n, tm = blockIdx.x / tiles_n, lane = threadIdx.x & 63;
     const int r = lane & 15, q = lane >> 4;
@@ -81,15 +84,16 @@ __global__ __launch_bounds__(64 * LIN_MAX_WAVES) void linear_small_fwd_kernel(co
     for (int v = 0; v < 4; ++v) {
         const int row = tm * 16 + 4 * q + v;
         float o = acc[v] + bv;
-        if (relu) o = o < 0.f ? 0.f : o;                        // NaN-preserving
+        if (act) o = dwc_act_simple(o, slope);                  // NaN-preserving
         if (row < M) y[(size_t)row * N + n] = o;
     }
 }
 
-// dx[M][K] = g[M][N] . w[N][K], g = dy (relu: dy where y > 0, else 0).  N % 16 == 0, K % 16 == 0.  One workgroup per 16 x 16 tile of dx.
+// dx[M][K] = g[M][N] . w[N][K], g = dy (yact given: dy where y > 0, else slope * dy; slope 0 = ReLU, 0.1 = LeakyReLU, whose output keeps
+// the sign of its input).  N % 16 == 0, K % 16 == 0.  One workgroup per 16 x 16 tile of dx.
 __global__ __launch_bounds__(64 * LIN_MAX_WAVES) void linear_small_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ yact,
                                                                                 const float* __restrict__ w, float* __restrict__ dx, int M,
-                                                                                int N, int K, int tiles_k) {
+                                                                                int N, int K, int tiles_k, float slope) {
     __shared__ float red[LIN_MAX_WAVES * 256];
     const int tk = blockIdx.x % tiles_k, tm = blockIdx.x / tiles_k, lane = threadIdx.x & 63;
     const int r = lane & 15, q = lane >> 4;
@@ -104,7 +108,7 @@ __global__ __launch_bounds__(64 * LIN_MAX_WAVES) void linear_small_dgrad_kernel(
             if (ya) {
                 const f32x4v yv = *reinterpret_cast<const f32x4v*>(ya + 16 * s);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) a[i] = yv[i] > 0.f ? a[i] : 0.f;
+                for (int i = 0; i < 4; ++i) a[i] = lin_act_grad(yv[i], a[i], slope);
             }
             return a;
         },
@@ -129,7 +133,7 @@ __global__ __launch_bounds__(64 * LIN_MAX_WAVES) void linear_small_dgrad_kernel(
 __global__ __launch_bounds__(64 * LIN_MAX_WAVES) void linear_small_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ yact,
                                                                                 const float* __restrict__ x, float* __restrict__ dw,
                                                                                 float* __restrict__ db, int M, int N, int K, int tiles_k,
-                                                                                int tiles) {
+                                                                                int tiles, float slope) {
     __shared__ float red[LIN_MAX_WAVES * 256];
     const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
     if ((int)blockIdx.x >= tiles) {                             // ---- bias gradient: columns 16 (blockIdx - tiles) ..
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(64 * LIN_MAX_WAVES) void linear_small_wgrad_kernel(
         for (int m = part; m < M; m += parts) {
             const size_t gi = (size_t)m * N + n;
             float gv = dy[gi];
-            if (yact) gv = yact[gi] > 0.f ? gv : 0.f;
+            if (yact) gv = lin_act_grad(yact[gi], gv, slope);
             s += gv;
         }
         red[part * 16 + r] = s;
@@ -163,7 +167,7 @@ __global__ __launch_bounds__(64 * LIN_MAX_WAVES) void linear_small_wgrad_kernel(
                 const int m = 16 * s + 4 * q + i;
                 const size_t gi = (size_t)min(m, M - 1) * N;
                 float gv = gcol[gi];
-                if (ycol) gv = ycol[gi] > 0.f ? gv : 0.f;
+                if (ycol) gv = lin_act_grad(ycol[gi], gv, slope);
                 a[i] = m < M ? gv : 0.f;
             }
             return a;
@@ -189,38 +193,68 @@ int linear_small_waves(int steps) { return std::max(1, std::min(LIN_MAX_WAVES, (
 
 bool linear_small_shape_ok(int M, int N, int K) { return M > 0 && N >= 16 && K >= 16 && !(N & 15) && !(K & 15) && M <= 4096; }
 
+bool linear_small_act_ok(int act) { return act == DWC_ACT_NONE || act == DWC_ACT_RELU || act == DWC_ACT_LRELU; }
+
+// LeakyReLU's slope is the caller's (the reference's Conv2dBlock has 0.1, networks.py:559, its LinearBlock 0.2, networks.py:614): finite
+// and in (0, 1), so that the output keeps the sign of the pre-activation and the backward can read the slope off it
+bool linear_small_slope_ok(int act, float slope) { return act != DWC_ACT_LRELU || (slope > 0.f && slope < 1.f); }
+
+int linear_small_fwd(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int act, float slope, void* stream) {
+    if (!x || !w || !y || !linear_small_shape_ok(M, N, K) || !linear_small_act_ok(act) || !linear_small_slope_ok(act, slope)) return DWC_EINVAL;
+    const int tiles_n = N / 16, tiles_m = (M + 15) / 16;
+    hipLaunchKernelGGL(linear_small_fwd_kernel, dim3(tiles_n * tiles_m), dim3(64 * linear_small_waves(K / 16)), 0, (hipStream_t)stream, x, w,
+                       bias, y, M, N, K, act, act == DWC_ACT_LRELU ? slope : 0.f, tiles_n);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+
+// y_act = the forward's output when it had an activation (act != none), else ignored
+int linear_small_bwd(const float* dy, const float* y_act, const float* x, const float* w, float* dx, float* dw, float* db, int M, int N, int K,
+                     int act, float lrelu_slope, void* stream) {
+    if (!dy || !x || !w || !linear_small_shape_ok(M, N, K) || !linear_small_act_ok(act) || !linear_small_slope_ok(act, lrelu_slope)) return DWC_EINVAL;
+    if (act == DWC_ACT_NONE) y_act = nullptr;
+    else if (!y_act) return DWC_EINVAL;
+    const float slope = act == DWC_ACT_LRELU ? lrelu_slope : 0.f;
+    hipStream_t st = (hipStream_t)stream;
+    if (dx) {
+        const int tiles_k = K / 16;
+        hipLaunchKernelGGL(linear_small_dgrad_kernel, dim3(tiles_k * ((M + 15) / 16)), dim3(64 * linear_small_waves(N / 16)), 0, st, dy,
+                           y_act, w, dx, M, N, K, tiles_k, slope);
+        DWC_LAUNCH_CHECK();
+    }
+    if (dw) {
+        const int tiles_k = K / 16, tiles = tiles_k * (N / 16);
+        hipLaunchKernelGGL(linear_small_wgrad_kernel, dim3(tiles + (db ? N / 16 : 0)), dim3(64 * linear_small_waves((M + 15) / 16)), 0, st,
+                           dy, y_act, x, dw, db, M, N, K, tiles_k, tiles, slope);
+        DWC_LAUNCH_CHECK();
+    }
+    return DWC_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int dwc_linear_small_ok(int M, int N, int K) { return linear_small_shape_ok(M, N, K) ? 1 : 0; }
 
-int dwc_linear_small_fwd(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int relu, void* stream) {
-    if (!x || !w || !y || !linear_small_shape_ok(M, N, K)) return DWC_EINVAL;
-    const int tiles_n = N / 16, tiles_m = (M + 15) / 16;
-    hipLaunchKernelGGL(linear_small_fwd_kernel, dim3(tiles_n * tiles_m), dim3(64 * linear_small_waves(K / 16)), 0, (hipStream_t)stream, x, w,
-                       bias, y, M, N, K, relu, tiles_n);
-    DWC_LAUNCH_CHECK();
-    return DWC_OK;
+int dwc_linear_small_fwd(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int act, void* stream) {
+    return linear_small_fwd(x, w, bias, y, M, N, K, act, 0.1f, stream);
 }
 
+int dwc_linear_small_fwd_act(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int act, float slope,
+                             void* stream) {
+    return linear_small_fwd(x, w, bias, y, M, N, K, act, slope, stream);
+}
+
+/* y_relu non-null: the forward had the ReLU */
 int dwc_linear_small_bwd(const float* dy, const float* y_relu, const float* x, const float* w, float* dx, float* dw, float* db, int M,
                          int N, int K, void* stream) {
-    if (!dy || !x || !w || !linear_small_shape_ok(M, N, K)) return DWC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    if (dx) {
-        const int tiles_k = K / 16;
-        hipLaunchKernelGGL(linear_small_dgrad_kernel, dim3(tiles_k * ((M + 15) / 16)), dim3(64 * linear_small_waves(N / 16)), 0, st, dy,
-                           y_relu, w, dx, M, N, K, tiles_k);
-        DWC_LAUNCH_CHECK();
-    }
-    if (dw) {
-        const int tiles_k = K / 16, tiles = tiles_k * (N / 16);
-        hipLaunchKernelGGL(linear_small_wgrad_kernel, dim3(tiles + (db ? N / 16 : 0)), dim3(64 * linear_small_waves((M + 15) / 16)), 0, st,
-                           dy, y_relu, x, dw, db, M, N, K, tiles_k, tiles);
-        DWC_LAUNCH_CHECK();
-    }
-    return DWC_OK;
+    return linear_small_bwd(dy, y_relu, x, w, dx, dw, db, M, N, K, y_relu ? DWC_ACT_RELU : DWC_ACT_NONE, 0.1f, stream);
+}
+
+int dwc_linear_small_bwd_act(const float* dy, const float* y_act, const float* x, const float* w, float* dx, float* dw, float* db, int M,
+                             int N, int K, int act, float slope, void* stream) {
+    return linear_small_bwd(dy, y_act, x, w, dx, dw, db, M, N, K, act, slope, stream);
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 //    variance, eps inside the sqrt, then weight[n,c]*xhat + bias[n,c]).
 //  * LayerNorm (reference networks.py:736-752: per-sample mean, UNBIASED std, divide by
 //    (std+eps), per-channel gamma/beta).
-//  * the ReLU that follows the norm in Conv2dBlock (networks.py:583-584) and ResBlock's
+//  * the ReLU / LeakyReLU(0.1) that follows the norm in Conv2dBlock (networks.py:583-584) and ResBlock's
 //    residual add (networks.py:521) are fused into the apply pass.
 //
 // All of these are HBM-bound: one statistics pass (16-byte loads, channels on the lanes so a
@@ -22,6 +22,34 @@
 #include "dwc_common.h"
 
 namespace {
+
+// The activation fused into the apply passes is one of none / ReLU / LeakyReLU(0.1) (DWC_ACT_NONE / _RELU / _LRELU), in the slope form
+// of dwc_act_simple; everything else is refused before any launch.
+bool norm_act_ok(int act) { return act == DWC_ACT_NONE || act == DWC_ACT_RELU || act == DWC_ACT_LRELU; }
+
+// The forward kernels other than ln_apply take the activation code at run time in the slope form of dwc_act_simple (same registers as
+// with the ReLU flag).  The backward kernels and ln_apply take the SLOPE as a template argument: LRELU = false is the code as it was,
+// runtime ReLU flag included, expression by expression -- and register by register (DESIGN.md has the compiler's resource report for
+// gfx950); LRELU = true is the same code with a factor 0.1 where ReLU has 0.  What was tried first: a runtime slope (a multiply and two
+// selects per element beside the resident plane) cost in_resident_bwd 16-27 registers, a wave per SIMD and spills at 512 threads; one
+// kernel per activation without the runtime flag scheduled the multi-pass kernels' loads further ahead, up to 30 registers more.  So
+// the multi-pass LRELU kernels keep the (always true) runtime flag, the resident one drops it, whichever the allocator likes better.
+// dy * act'(pre), pre recomputed by the caller with the forward's own expression and rounding: an element within an ulp of zero gets the
+// slope its forward output got
+// (LeakyReLU as ONE multiply by a selected factor, g * 1 being g: written as pre > 0 ? g : 0.1 * g the scheduler computes 0.1 * g of every
+// resident element ahead of the selects -- 27 more registers in in_resident_bwd)
+template <bool LRELU> __device__ __forceinline__ float norm_act_grad(float pre, float g) {
+    if constexpr (LRELU) return g * (pre > 0.f ? 1.f : 0.1f);
+    else return pre > 0.f ? g : 0.f;
+}
+
+// launch of KERNEL<TARGS..., act is LeakyReLU>; TARGS = the other template arguments in parentheses
+#define NORM_TARGS(...) __VA_ARGS__
+#define NORM_LAUNCH_ACT(act, KERNEL, TARGS, ...)                                                          \
+    do {                                                                                                   \
+        if ((act) == DWC_ACT_LRELU) hipLaunchKernelGGL((KERNEL<NORM_TARGS TARGS, true>), __VA_ARGS__);    \
+        else hipLaunchKernelGGL((KERNEL<NORM_TARGS TARGS, false>), __VA_ARGS__);                          \
+    } while (0)
 
 // rows-per-sample are split into `chunks`; geometry shared by the statistics kernels (one partial per chunk)
 struct RowSplit {
@@ -209,9 +237,10 @@ template <typename T>
 __global__ __launch_bounds__(256) void in_apply(const T* __restrict__ x, const float* __restrict__ mean,
                                                 const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                 const float* __restrict__ beta, const T* __restrict__ residual,
-                                                T* __restrict__ y, int HW, int C, int rows_per_chunk, int relu,
+                                                T* __restrict__ y, int HW, int C, int rows_per_chunk, int act,
                                                 unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
     constexpr int V = VecOf<T>::V;
+    const float slope = dwc_act_slope(act);
     const int cq = C / V;
     const int groups = 256 / cq;
     const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
@@ -238,7 +267,7 @@ __global__ __launch_bounds__(256) void in_apply(const T* __restrict__ x, const f
 #pragma unroll
         for (int k = 0; k < V; ++k) {
             float t = (v[k] - mu[k]) * sc[k] + sh[k];
-            if (relu) t = t < 0.f ? 0.f : t;              // NaN-preserving
+            if (act) t = dwc_act_simple(t, slope);        // NaN-preserving; -0.0 passes
             o[k] = res ? t + res[k] : t;
         }
         if constexpr (std::is_same<T, float>::value) am = dwc_amax_fold<V>(am, o);
@@ -272,12 +301,12 @@ __global__ __launch_bounds__(256) void in_apply(const T* __restrict__ x, const f
     }
 }
 
-template <typename T>
+template <typename T, bool LRELU>
 __global__ __launch_bounds__(256) void in_bwd_partial(const T* __restrict__ dy, const T* __restrict__ x,
                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       float* __restrict__ part, int HW, int C, int rows_per_chunk, size_t plane,
-                                                      int relu) {
+                                                      int act) {
     constexpr int V = VecOf<T>::V;
     __shared__ float sm[2 * 256 * V];
     const int cq = C / V;
@@ -304,8 +333,8 @@ __global__ __launch_bounds__(256) void in_bwd_partial(const T* __restrict__ dy, 
             const float xh = (xv[k] - mu[k]) * rs[k];
             float g = dv[k];
             // (the forward's own expression and rounding, (x - mu) * (gamma * rstd) + beta: an element within an ulp of zero must get the
-            // mask its forward output got)
-            if (relu) g = ((xv[k] - mu[k]) * (ga[k] * rs[k]) + be[k]) > 0.f ? g : 0.f;
+            // slope its forward output got)
+            if (act) g = norm_act_grad<LRELU>((xv[k] - mu[k]) * (ga[k] * rs[k]) + be[k], g);
             s1[k] += g;
             s2[k] += g * xh;
         }
@@ -337,12 +366,12 @@ __global__ __launch_bounds__(256) void in_bwd_partial(const T* __restrict__ dy, 
     }
 }
 
-template <typename T>
+template <typename T, bool LRELU>
 __global__ __launch_bounds__(256) void in_bwd_apply(const T* __restrict__ dy, const T* __restrict__ x,
                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
                                                     const float* __restrict__ sums, T* __restrict__ dx, int HW, int C, int BC,
-                                                    int rows_per_chunk, int relu, unsigned long long* amax = nullptr,
+                                                    int rows_per_chunk, int act, unsigned long long* amax = nullptr,
                                                     unsigned amax_ep = 0) {
     constexpr int V = VecOf<T>::V;
     const int cq = C / V;
@@ -373,8 +402,8 @@ __global__ __launch_bounds__(256) void in_bwd_apply(const T* __restrict__ dy, co
             const float xh = (xv[k] - mu[k]) * rs[k];
             float g = dv[k];
             // (the forward's own expression and rounding, (x - mu) * (gamma * rstd) + beta: an element within an ulp of zero must get the
-            // mask its forward output got)
-            if (relu) g = ((xv[k] - mu[k]) * (ga[k] * rs[k]) + be[k]) > 0.f ? g : 0.f;
+            // slope its forward output got)
+            if (act) g = norm_act_grad<LRELU>((xv[k] - mu[k]) * (ga[k] * rs[k]) + be[k], g);
             o[k] = ga[k] * rs[k] * (g - k1[k] - xh * k2[k]);
         }
         if constexpr (std::is_same<T, float>::value) am = dwc_amax_fold<V>(am, o);
@@ -400,7 +429,8 @@ __global__ __launch_bounds__(256) void in_bwd_apply(const T* __restrict__ dy, co
         ldv(dy, i0, d0);
         one(x0, d0, o0);
         stv(dx, i0, o0);
-    }    if constexpr (std::is_same<T, float>::value) {      // (every thread of the block gets here: C is a power of two, groups * cq == 256)
+    }
+    if constexpr (std::is_same<T, float>::value) {      // (every thread of the block gets here: C is a power of two, groups * cq == 256)
         __shared__ unsigned s_am[4];
         dwc_amax_block_publish(amax, amax_ep, am, s_am);
     }
@@ -482,11 +512,11 @@ __global__ void ln_stats_final(const T* __restrict__ x, const float* __restrict_
     inv[n] = (float)(1.0 / (sqrt(var) + (double)eps));
 }
 
-template <typename T>
+template <typename T, bool LRELU>
 __global__ __launch_bounds__(256) void ln_apply(const T* __restrict__ x, const float* __restrict__ mean,
                                                 const float* __restrict__ inv, const float* __restrict__ gamma,
                                                 const float* __restrict__ beta, T* __restrict__ y, int HW, int C, int rows_per_chunk,
-                                                int relu, unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
+                                                int act, unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
     constexpr int V = VecOf<T>::V;
     const int cq = C / V;
     const int groups = 256 / cq;
@@ -507,7 +537,7 @@ __global__ __launch_bounds__(256) void ln_apply(const T* __restrict__ x, const f
 #pragma unroll
         for (int k = 0; k < V; ++k) {
             const float t = (v[k] - mu) * sc[k] + sh[k];
-            o[k] = (relu && t < 0.f) ? 0.f : t;          // NaN-preserving
+            o[k] = (act && t < 0.f) ? (LRELU ? 0.1f * t : 0.f) : t;          // NaN-preserving; -0.0 passes
         }
         if constexpr (std::is_same<T, float>::value) am = dwc_amax_fold<V>(am, o);
     };
@@ -536,12 +566,12 @@ __global__ __launch_bounds__(256) void ln_apply(const T* __restrict__ x, const f
 
 // per block: sample sums (sum g, sum g*(x-mu)) with g = dy_eff*gamma, and per-channel
 // partials of dgamma (dy_eff*xhat) and dbeta (dy_eff)
-template <typename T>
+template <typename T, bool LRELU>
 __global__ __launch_bounds__(256) void ln_bwd_partial(const T* __restrict__ dy, const T* __restrict__ x,
                                                       const float* __restrict__ mean, const float* __restrict__ inv,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       float* __restrict__ part_s, float* __restrict__ part_c, int HW, int C,
-                                                      int rows_per_chunk, int relu) {
+                                                      int rows_per_chunk, int act) {
     constexpr int V = VecOf<T>::V;
     __shared__ float sm[2 * 256 * V];
     __shared__ float sr[4];
@@ -567,7 +597,7 @@ __global__ __launch_bounds__(256) void ln_bwd_partial(const T* __restrict__ dy, 
             const float xc = xv[k] - mu;
             const float xh = xc * iv;
             float d = dv[k];
-            if (relu) d = (xc * (ga[k] * iv) + be[k]) > 0.f ? d : 0.f;      // (the forward's expression and rounding: ln_apply)
+            if (act) d = norm_act_grad<LRELU>(xc * (ga[k] * iv) + be[k], d);   // (the forward's expression and rounding: ln_apply)
             dg[k] += d * xh;
             db[k] += d;
             const float g = d * ga[k];
@@ -676,12 +706,12 @@ __global__ __launch_bounds__(1024) void ln_bwd_final(const float* __restrict__ p
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void ln_bwd_apply(const T* __restrict__ dy, const T* __restrict__ x,
+template <typename T, bool LRELU>
+__global__ __launch_bounds__(256, LRELU && sizeof(T) == 4 ? 7 : 1) void ln_bwd_apply(const T* __restrict__ dy, const T* __restrict__ x,
                                                     const float* __restrict__ mean, const float* __restrict__ inv,
                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
                                                     const float* __restrict__ sums, T* __restrict__ dx, int HW, int C,
-                                                    int rows_per_chunk, float eps, int relu, unsigned long long* amax = nullptr,
+                                                    int rows_per_chunk, float eps, int act, unsigned long long* amax = nullptr,
                                                     unsigned amax_ep = 0) {
     constexpr int V = VecOf<T>::V;
     const int cq = C / V;
@@ -707,7 +737,7 @@ __global__ __launch_bounds__(256) void ln_bwd_apply(const T* __restrict__ dy, co
         for (int k = 0; k < V; ++k) {
             const float xc = xv[k] - mu;
             float d = dv[k];
-            if (relu) d = (xc * (ga[k] * iv) + be[k]) > 0.f ? d : 0.f;      // (the forward's expression and rounding: ln_apply)
+            if (act) d = norm_act_grad<LRELU>(xc * (ga[k] * iv) + be[k], d);   // (the forward's expression and rounding: ln_apply)
             o[k] = (d * ga[k] - mean_g) * iv - xc * k2;
         }
         if constexpr (std::is_same<T, float>::value) am = dwc_amax_fold<V>(am, o);
@@ -733,7 +763,8 @@ __global__ __launch_bounds__(256) void ln_bwd_apply(const T* __restrict__ dy, co
         ldv(dy, i0, d0);
         one(x0, d0, o0);
         stv(dx, i0, o0);
-    }    if constexpr (std::is_same<T, float>::value) {      // (every thread of the block gets here: C is a power of two, groups * cq == 256)
+    }
+    if constexpr (std::is_same<T, float>::value) {      // (every thread of the block gets here: C is a power of two, groups * cq == 256)
         __shared__ unsigned s_am[4];
         dwc_amax_block_publish(amax, amax_ep, am, s_am);
     }
@@ -842,9 +873,10 @@ template <typename T, int HW, int THREADS, bool HAS_RES>
 __global__ __launch_bounds__(THREADS) void in_resident_fwd(const T* __restrict__ x, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, const T* __restrict__ residual,
                                                                T* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd,
-                                                               int C, float eps, int relu, int pairs, unsigned long long* amax = nullptr,
+                                                               int C, float eps, int act, int pairs, unsigned long long* amax = nullptr,
                                                                unsigned amax_ep = 0) {
     constexpr int V = 4, CQ = Raw4<T>::CQ, ROWS = THREADS / CQ, NP = HW / ROWS;
+    const float slope = dwc_act_slope(act);
     typedef typename Raw4<T>::type Raw;
     __shared__ float sm[(THREADS / 64) * CQ * 2 * V];
     const int cqt = C / V;                                                       // 4-channel pieces per pixel of the tensor
@@ -916,7 +948,7 @@ __global__ __launch_bounds__(THREADS) void in_resident_fwd(const T* __restrict__
 #pragma unroll
         for (int k = 0; k < V; ++k) {
             float t = (v[k] - mu[k]) * sc[k] + sh[k];
-            if (relu) t = t < 0.f ? 0.f : t;              // NaN-preserving
+            if (act) t = dwc_act_simple(t, slope);        // NaN-preserving; -0.0 passes
             o[k] = HAS_RES ? t + q[k] : t;
         }
         if constexpr (std::is_same<T, float>::value) am = dwc_amax_fold<V>(am, o);
@@ -930,12 +962,12 @@ __global__ __launch_bounds__(THREADS) void in_resident_fwd(const T* __restrict__
     }
 }
 
-template <typename T, int HW, int THREADS>
+template <typename T, int HW, int THREADS, bool LRELU>
 __global__ __launch_bounds__(THREADS, THREADS >= 512 ? 4 : 1) void in_resident_bwd(const T* __restrict__ dy, const T* __restrict__ x,
                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                T* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                               int C, int relu, int pairs, unsigned long long* amax = nullptr,
+                                                               int C, int act, int pairs, unsigned long long* amax = nullptr,
                                                                unsigned amax_ep = 0) {
     constexpr int V = 4, CQ = Raw4<T>::CQ, ROWS = THREADS / CQ, NP = HW / ROWS;
     typedef typename Raw4<T>::type Raw;
@@ -966,6 +998,7 @@ __global__ __launch_bounds__(THREADS, THREADS >= 512 ? 4 : 1) void in_resident_b
     float s[2 * V];
 #pragma unroll
     for (int k = 0; k < 2 * V; ++k) s[k] = 0.f;
+    unsigned am = 0;
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
         float xv[V], dv[V];
@@ -976,8 +1009,8 @@ __global__ __launch_bounds__(THREADS, THREADS >= 512 ? 4 : 1) void in_resident_b
             const float xh = (xv[k] - mu[k]) * rs[k];
             float g = dv[k];
             // (the forward's own expression and rounding, (x - mu) * (gamma * rstd) + beta: an element within an ulp of zero must get the
-            // mask its forward output got)
-            if (relu) g = ((xv[k] - mu[k]) * (ga[k] * rs[k]) + be[k]) > 0.f ? g : 0.f;
+            // slope its forward output got)
+            if (LRELU || act) g = norm_act_grad<LRELU>((xv[k] - mu[k]) * (ga[k] * rs[k]) + be[k], g);
             s[k] += g;
             s[V + k] += g * xh;
         }
@@ -992,7 +1025,6 @@ __global__ __launch_bounds__(THREADS, THREADS >= 512 ? 4 : 1) void in_resident_b
     }
     const float inv = 1.f / (float)HW;
     char* ob = reinterpret_cast<char*>(dx) + ubase;
-    unsigned am = 0;
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
         float xv[V], dv[V], o[V];
@@ -1003,8 +1035,8 @@ __global__ __launch_bounds__(THREADS, THREADS >= 512 ? 4 : 1) void in_resident_b
             const float xh = (xv[k] - mu[k]) * rs[k];
             float g = dv[k];
             // (the forward's own expression and rounding, (x - mu) * (gamma * rstd) + beta: an element within an ulp of zero must get the
-            // mask its forward output got)
-            if (relu) g = ((xv[k] - mu[k]) * (ga[k] * rs[k]) + be[k]) > 0.f ? g : 0.f;
+            // slope its forward output got)
+            if (LRELU || act) g = norm_act_grad<LRELU>((xv[k] - mu[k]) * (ga[k] * rs[k]) + be[k], g);
             o[k] = ga[k] * rs[k] * (g - s[k] * inv - xh * (s[V + k] * inv));
         }
         if constexpr (std::is_same<T, float>::value) am = dwc_amax_fold<V>(am, o);
@@ -1037,9 +1069,9 @@ size_t instnorm_ws_bytes(int B, int HW, int C) {
 
 template <typename T>
 int instnorm_fwd_t(const T* x, const float* gamma, const float* beta, const T* residual, T* y, float* mean,
-                     float* rstd, int B, int HW, int C, float eps, int relu, void* ws, size_t ws_bytes, void* stream,
+                     float* rstd, int B, int HW, int C, float eps, int act, void* ws, size_t ws_bytes, void* stream,
                      unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
-    if (!norm_shape_ok(B, HW, C, VecOf<T>::V)) return DWC_EINVAL;
+    if (!norm_shape_ok(B, HW, C, VecOf<T>::V) || !norm_act_ok(act)) return DWC_EINVAL;
     if (!ws || ws_bytes < instnorm_ws_bytes(B, HW, C)) return DWC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (const int rhw = in_resident_hw<T>(HW, C)) {          // small planes: one pass, plane resident in registers
@@ -1049,11 +1081,11 @@ int instnorm_fwd_t(const T* x, const float* gamma, const float* beta, const T* r
         // threads 81.8 against 89.0 on 1 024; fp32 without a residual: 256 threads 16.1 us, 512 threads 16.7.  Whole 128-byte lines per
         // workgroup (64 bf16 channels, 1 024 threads, no pairing of workgroups over a line): 52.2 against 54.9 us -- not what holds these
         // kernels at 2.4 TB/s; not kept)
-        if (rhw == 1024 && !residual && sizeof(T) == 2) hipLaunchKernelGGL((in_resident_fwd<T, 1024, 512, false>), grid, dim3(512), 0, st, x, gamma, beta, residual, y, mean, rstd, C, eps, relu, pairs, amax, amax_ep);
-        else if (rhw == 1024 && residual) hipLaunchKernelGGL((in_resident_fwd<T, 1024, 512, true>), grid, dim3(512), 0, st, x, gamma, beta, residual, y, mean, rstd, C, eps, relu, pairs, amax, amax_ep);
-        else if (rhw == 1024) hipLaunchKernelGGL((in_resident_fwd<T, 1024, 256, false>), grid, dim3(256), 0, st, x, gamma, beta, residual, y, mean, rstd, C, eps, relu, pairs, amax, amax_ep);
-        else if (residual) hipLaunchKernelGGL((in_resident_fwd<T, 256, 256, true>), grid, dim3(256), 0, st, x, gamma, beta, residual, y, mean, rstd, C, eps, relu, pairs, amax, amax_ep);
-        else hipLaunchKernelGGL((in_resident_fwd<T, 256, 256, false>), grid, dim3(256), 0, st, x, gamma, beta, residual, y, mean, rstd, C, eps, relu, pairs, amax, amax_ep);
+        if (rhw == 1024 && !residual && sizeof(T) == 2) hipLaunchKernelGGL((in_resident_fwd<T, 1024, 512, false>), grid, dim3(512), 0, st, x, gamma, beta, residual, y, mean, rstd, C, eps, act, pairs, amax, amax_ep);
+        else if (rhw == 1024 && residual) hipLaunchKernelGGL((in_resident_fwd<T, 1024, 512, true>), grid, dim3(512), 0, st, x, gamma, beta, residual, y, mean, rstd, C, eps, act, pairs, amax, amax_ep);
+        else if (rhw == 1024) hipLaunchKernelGGL((in_resident_fwd<T, 1024, 256, false>), grid, dim3(256), 0, st, x, gamma, beta, residual, y, mean, rstd, C, eps, act, pairs, amax, amax_ep);
+        else if (residual) hipLaunchKernelGGL((in_resident_fwd<T, 256, 256, true>), grid, dim3(256), 0, st, x, gamma, beta, residual, y, mean, rstd, C, eps, act, pairs, amax, amax_ep);
+        else hipLaunchKernelGGL((in_resident_fwd<T, 256, 256, false>), grid, dim3(256), 0, st, x, gamma, beta, residual, y, mean, rstd, C, eps, act, pairs, amax, amax_ep);
         DWC_LAUNCH_CHECK();
         return DWC_OK;
     }
@@ -1066,16 +1098,16 @@ int instnorm_fwd_t(const T* x, const float* gamma, const float* beta, const T* r
     DWC_LAUNCH_CHECK();
     const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
     hipLaunchKernelGGL(in_apply<T>, dim3(ra.chunks, B), dim3(256), 0, st, x, mean, rstd, gamma, beta, residual, y, HW, C,
-                       ra.rows_per_chunk, relu, amax, amax_ep);
+                       ra.rows_per_chunk, act, amax, amax_ep);
     DWC_LAUNCH_CHECK();
     return DWC_OK;
 }
 
 template <typename T>
 int instnorm_bwd_t(const T* dy, const T* x, const float* mean, const float* rstd, const float* gamma,
-                   const float* beta, T* dx, float* dgamma, float* dbeta, int B, int HW, int C, int relu, void* ws,
+                   const float* beta, T* dx, float* dgamma, float* dbeta, int B, int HW, int C, int act, void* ws,
                      size_t ws_bytes, void* stream, unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
-    if (!norm_shape_ok(B, HW, C, VecOf<T>::V)) return DWC_EINVAL;
+    if (!norm_shape_ok(B, HW, C, VecOf<T>::V) || !norm_act_ok(act)) return DWC_EINVAL;
     if (!ws || ws_bytes < instnorm_ws_bytes(B, HW, C)) return DWC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (const int rhw = in_resident_hw<T>(HW, C)) {
@@ -1085,9 +1117,9 @@ int instnorm_bwd_t(const T* dy, const T* x, const float* mean, const float* rstd
         // two-stage reduction alone, 98.2 with 1024 threads -- 8 pieces per thread and tensor, no spills; fp32 31.2 -> 25.4 with the
         // reduction alone, 26.1 with 1024 threads)
         constexpr bool wide = sizeof(T) == 2;
-        if (rhw == 1024 && wide) hipLaunchKernelGGL((in_resident_bwd<T, 1024, 1024>), grid, dim3(1024), 0, st, dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, C, relu, pairs, amax, amax_ep);
-        else if (rhw == 1024) hipLaunchKernelGGL((in_resident_bwd<T, 1024, 512>), grid, dim3(512), 0, st, dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, C, relu, pairs, amax, amax_ep);
-        else hipLaunchKernelGGL((in_resident_bwd<T, 256, 256>), grid, dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, C, relu, pairs, amax, amax_ep);
+        if (rhw == 1024 && wide) NORM_LAUNCH_ACT(act, in_resident_bwd, (T, 1024, 1024), grid, dim3(1024), 0, st, dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, C, act, pairs, amax, amax_ep);
+        else if (rhw == 1024) NORM_LAUNCH_ACT(act, in_resident_bwd, (T, 1024, 512), grid, dim3(512), 0, st, dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, C, act, pairs, amax, amax_ep);
+        else NORM_LAUNCH_ACT(act, in_resident_bwd, (T, 256, 256), grid, dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, C, act, pairs, amax, amax_ep);
         DWC_LAUNCH_CHECK();
         return DWC_OK;
     }
@@ -1095,14 +1127,14 @@ int instnorm_bwd_t(const T* dy, const T* x, const float* mean, const float* rstd
     const size_t plane = (size_t)B * rs.chunks * C;
     float* part = (float*)ws;
     float* sums = part + 2 * plane;
-    hipLaunchKernelGGL(in_bwd_partial<T>, dim3(rs.chunks, B), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, part, HW, C,
-                       rs.rows_per_chunk, plane, relu);
+    NORM_LAUNCH_ACT(act, in_bwd_partial, (T), dim3(rs.chunks, B), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, part, HW, C,
+                    rs.rows_per_chunk, plane, act);
     DWC_LAUNCH_CHECK();
     hipLaunchKernelGGL(in_bwd_final_wide, dim3((C + 63) / 64, B), dim3(256), 0, st, part, sums, dgamma, dbeta, B * C, C, rs.chunks, plane);
     DWC_LAUNCH_CHECK();
     const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
-    hipLaunchKernelGGL(in_bwd_apply<T>, dim3(ra.chunks, B), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, sums, dx, HW, C,
-                       B * C, ra.rows_per_chunk, relu, amax, amax_ep);
+    NORM_LAUNCH_ACT(act, in_bwd_apply, (T), dim3(ra.chunks, B), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, sums, dx, HW, C,
+                    B * C, ra.rows_per_chunk, act, amax, amax_ep);
     DWC_LAUNCH_CHECK();
     return DWC_OK;
 }
@@ -1114,9 +1146,9 @@ size_t layernorm_ws_bytes(int B, int HW, int C) {
 
 template <typename T>
 int layernorm_fwd_t(const T* x, const float* gamma, const float* beta, T* y, float* mean, float* inv, int B, int HW,
-                      int C, float eps, int relu, void* ws, size_t ws_bytes, void* stream, unsigned long long* amax = nullptr,
+                      int C, float eps, int act, void* ws, size_t ws_bytes, void* stream, unsigned long long* amax = nullptr,
                       unsigned amax_ep = 0) {
-    if (!norm_shape_ok(B, HW, C, VecOf<T>::V) || (size_t)HW * C < 2) return DWC_EINVAL;
+    if (!norm_shape_ok(B, HW, C, VecOf<T>::V) || (size_t)HW * C < 2 || !norm_act_ok(act)) return DWC_EINVAL;
     if (!ws || ws_bytes < layernorm_ws_bytes(B, HW, C)) return DWC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const RowSplit rs = plan_rows(B, HW);
@@ -1126,32 +1158,32 @@ int layernorm_fwd_t(const T* x, const float* gamma, const float* beta, T* y, flo
     hipLaunchKernelGGL(ln_stats_final<T>, dim3((B + 63) / 64), dim3(64), 0, st, x, part, mean, inv, B, HW, C, rs.chunks, eps);
     DWC_LAUNCH_CHECK();
     const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
-    hipLaunchKernelGGL(ln_apply<T>, dim3(ra.chunks, B), dim3(256), 0, st, x, mean, inv, gamma, beta, y, HW, C, ra.rows_per_chunk, relu,
-                       amax, amax_ep);
+    NORM_LAUNCH_ACT(act, ln_apply, (T), dim3(ra.chunks, B), dim3(256), 0, st, x, mean, inv, gamma, beta, y, HW, C, ra.rows_per_chunk,
+                    act, amax, amax_ep);
     DWC_LAUNCH_CHECK();
     return DWC_OK;
 }
 
 template <typename T>
 int layernorm_bwd_t(const T* dy, const T* x, const float* mean, const float* inv, const float* gamma,
-                    const float* beta, T* dx, float* dgamma, float* dbeta, int B, int HW, int C, float eps, int relu,
+                    const float* beta, T* dx, float* dgamma, float* dbeta, int B, int HW, int C, float eps, int act,
                       void* ws, size_t ws_bytes, void* stream, unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
-    if (!norm_shape_ok(B, HW, C, VecOf<T>::V)) return DWC_EINVAL;
+    if (!norm_shape_ok(B, HW, C, VecOf<T>::V) || !norm_act_ok(act)) return DWC_EINVAL;
     if (!ws || ws_bytes < layernorm_ws_bytes(B, HW, C)) return DWC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const RowSplit rs = plan_rows(B, HW);
     float* part_s = (float*)ws;
     float* part_c = part_s + (size_t)B * rs.chunks * 2;
     float* sums = part_c + (size_t)B * rs.chunks * 2 * C;
-    hipLaunchKernelGGL(ln_bwd_partial<T>, dim3(rs.chunks, B), dim3(256), 0, st, dy, x, mean, inv, gamma, beta, part_s, part_c, HW,
-                       C, rs.rows_per_chunk, relu);
+    NORM_LAUNCH_ACT(act, ln_bwd_partial, (T), dim3(rs.chunks, B), dim3(256), 0, st, dy, x, mean, inv, gamma, beta, part_s, part_c, HW,
+                    C, rs.rows_per_chunk, act);
     DWC_LAUNCH_CHECK();
     hipLaunchKernelGGL(ln_bwd_final, dim3(B + (C + 63) / 64), dim3(1024), 0, st, part_s, part_c, sums, dgamma, dbeta, B, C,
                        rs.chunks);
     DWC_LAUNCH_CHECK();
     const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
-    hipLaunchKernelGGL(ln_bwd_apply<T>, dim3(ra.chunks, B), dim3(256), 0, st, dy, x, mean, inv, gamma, beta, sums, dx, HW, C,
-                       ra.rows_per_chunk, eps, relu, amax, amax_ep);
+    NORM_LAUNCH_ACT(act, ln_bwd_apply, (T), dim3(ra.chunks, B), dim3(256), 0, st, dy, x, mean, inv, gamma, beta, sums, dx, HW, C,
+                    ra.rows_per_chunk, eps, act, amax, amax_ep);
     DWC_LAUNCH_CHECK();
     return DWC_OK;
 }
@@ -1635,77 +1667,80 @@ int dwc_bf16_batchnorm_bwd(const void* dy, const void* x, const float* mean, con
                                      Bs, HW, C, act, training, ws, ws_bytes, stream);
 }
 
+/* 1 when `act` is an activation code the instance-norm / layer-norm / linear_small entry points fuse (host only, no launch) */
+int dwc_norm_act_ok(int act) { return norm_act_ok(act) ? 1 : 0; }
+
 size_t dwc_instnorm_ws_bytes(int B, int HW, int C) { return instnorm_ws_bytes(B, HW, C); }
 size_t dwc_layernorm_ws_bytes(int B, int HW, int C) { return layernorm_ws_bytes(B, HW, C); }
 
 int dwc_instnorm_fwd(const float* x, const float* gamma, const float* beta, const float* residual, float* y, float* mean,
-                     float* rstd, int B, int HW, int C, float eps, int relu, void* ws, size_t ws_bytes, void* stream) {
-    return instnorm_fwd_t<float>(x, gamma, beta, residual, y, mean, rstd, B, HW, C, eps, relu, ws, ws_bytes, stream);
+                     float* rstd, int B, int HW, int C, float eps, int act, void* ws, size_t ws_bytes, void* stream) {
+    return instnorm_fwd_t<float>(x, gamma, beta, residual, y, mean, rstd, B, HW, C, eps, act, ws, ws_bytes, stream);
 }
 int dwc_instnorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                     const float* beta, float* dx, float* dgamma, float* dbeta, int B, int HW, int C, int relu, void* ws,
+                     const float* beta, float* dx, float* dgamma, float* dbeta, int B, int HW, int C, int act, void* ws,
                      size_t ws_bytes, void* stream) {
-    return instnorm_bwd_t<float>(dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, B, HW, C, relu, ws, ws_bytes, stream);
+    return instnorm_bwd_t<float>(dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, B, HW, C, act, ws, ws_bytes, stream);
 }
 int dwc_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* inv, int B, int HW,
-                      int C, float eps, int relu, void* ws, size_t ws_bytes, void* stream) {
-    return layernorm_fwd_t<float>(x, gamma, beta, y, mean, inv, B, HW, C, eps, relu, ws, ws_bytes, stream);
+                      int C, float eps, int act, void* ws, size_t ws_bytes, void* stream) {
+    return layernorm_fwd_t<float>(x, gamma, beta, y, mean, inv, B, HW, C, eps, act, ws, ws_bytes, stream);
 }
 int dwc_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* inv, const float* gamma,
-                      const float* beta, float* dx, float* dgamma, float* dbeta, int B, int HW, int C, float eps, int relu,
+                      const float* beta, float* dx, float* dgamma, float* dbeta, int B, int HW, int C, float eps, int act,
                       void* ws, size_t ws_bytes, void* stream) {
-    return layernorm_bwd_t<float>(dy, x, mean, inv, gamma, beta, dx, dgamma, dbeta, B, HW, C, eps, relu, ws, ws_bytes, stream);
+    return layernorm_bwd_t<float>(dy, x, mean, inv, gamma, beta, dx, dgamma, dbeta, B, HW, C, eps, act, ws, ws_bytes, stream);
 }
 
 /* The same four with the absmax slot of the tensor they WRITE (y / dx): raised by atomic max on (epoch << 32 | magnitude bits) from
  * the apply pass, so that a two-plane split-product convolution (dwc_h2_*, include/dwcgan_hip.h) that consumes the tensor needs no
  * dwc_absmax pass of its own.  out_amax NULL: exactly the plain entry point. */
 int dwc_instnorm_fwd_amax(const float* x, const float* gamma, const float* beta, const float* residual, float* y, float* mean,
-                          float* rstd, int B, int HW, int C, float eps, int relu, void* ws, size_t ws_bytes,
+                          float* rstd, int B, int HW, int C, float eps, int act, void* ws, size_t ws_bytes,
                           void* out_amax, unsigned out_epoch, void* stream) {
-    return instnorm_fwd_t<float>(x, gamma, beta, residual, y, mean, rstd, B, HW, C, eps, relu, ws, ws_bytes, stream,
+    return instnorm_fwd_t<float>(x, gamma, beta, residual, y, mean, rstd, B, HW, C, eps, act, ws, ws_bytes, stream,
                                  (unsigned long long*)out_amax, out_epoch);
 }
 int dwc_instnorm_bwd_amax(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                          const float* beta, float* dx, float* dgamma, float* dbeta, int B, int HW, int C, int relu, void* ws,
+                          const float* beta, float* dx, float* dgamma, float* dbeta, int B, int HW, int C, int act, void* ws,
                           size_t ws_bytes, void* out_amax, unsigned out_epoch, void* stream) {
-    return instnorm_bwd_t<float>(dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, B, HW, C, relu, ws, ws_bytes, stream,
+    return instnorm_bwd_t<float>(dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, B, HW, C, act, ws, ws_bytes, stream,
                                  (unsigned long long*)out_amax, out_epoch);
 }
 int dwc_layernorm_fwd_amax(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* inv, int B, int HW,
-                           int C, float eps, int relu, void* ws, size_t ws_bytes, void* out_amax, unsigned out_epoch, void* stream) {
-    return layernorm_fwd_t<float>(x, gamma, beta, y, mean, inv, B, HW, C, eps, relu, ws, ws_bytes, stream, (unsigned long long*)out_amax,
+                           int C, float eps, int act, void* ws, size_t ws_bytes, void* out_amax, unsigned out_epoch, void* stream) {
+    return layernorm_fwd_t<float>(x, gamma, beta, y, mean, inv, B, HW, C, eps, act, ws, ws_bytes, stream, (unsigned long long*)out_amax,
                                   out_epoch);
 }
 int dwc_layernorm_bwd_amax(const float* dy, const float* x, const float* mean, const float* inv, const float* gamma,
-                           const float* beta, float* dx, float* dgamma, float* dbeta, int B, int HW, int C, float eps, int relu,
+                           const float* beta, float* dx, float* dgamma, float* dbeta, int B, int HW, int C, float eps, int act,
                            void* ws, size_t ws_bytes, void* out_amax, unsigned out_epoch, void* stream) {
-    return layernorm_bwd_t<float>(dy, x, mean, inv, gamma, beta, dx, dgamma, dbeta, B, HW, C, eps, relu, ws, ws_bytes, stream,
+    return layernorm_bwd_t<float>(dy, x, mean, inv, gamma, beta, dx, dgamma, dbeta, B, HW, C, eps, act, ws, ws_bytes, stream,
                                   (unsigned long long*)out_amax, out_epoch);
 }
 
 /* bf16 activations (x, residual, y, dy, dx); statistics, gamma/beta and their gradients stay fp32 */
 int dwc_bf16_instnorm_fwd(const void* x, const float* gamma, const float* beta, const void* residual, void* y, float* mean,
-                          float* rstd, int B, int HW, int C, float eps, int relu, void* ws, size_t ws_bytes, void* stream) {
+                          float* rstd, int B, int HW, int C, float eps, int act, void* ws, size_t ws_bytes, void* stream) {
     return instnorm_fwd_t<dwc_bf16>((const dwc_bf16*)x, gamma, beta, (const dwc_bf16*)residual, (dwc_bf16*)y, mean, rstd, B, HW, C,
-                                    eps, relu, ws, ws_bytes, stream);
+                                    eps, act, ws, ws_bytes, stream);
 }
 int dwc_bf16_instnorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
-                          const float* beta, void* dx, float* dgamma, float* dbeta, int B, int HW, int C, int relu, void* ws,
+                          const float* beta, void* dx, float* dgamma, float* dbeta, int B, int HW, int C, int act, void* ws,
                           size_t ws_bytes, void* stream) {
     return instnorm_bwd_t<dwc_bf16>((const dwc_bf16*)dy, (const dwc_bf16*)x, mean, rstd, gamma, beta, (dwc_bf16*)dx, dgamma, dbeta,
-                                    B, HW, C, relu, ws, ws_bytes, stream);
+                                    B, HW, C, act, ws, ws_bytes, stream);
 }
 int dwc_bf16_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* inv, int B,
-                           int HW, int C, float eps, int relu, void* ws, size_t ws_bytes, void* stream) {
-    return layernorm_fwd_t<dwc_bf16>((const dwc_bf16*)x, gamma, beta, (dwc_bf16*)y, mean, inv, B, HW, C, eps, relu, ws, ws_bytes,
+                           int HW, int C, float eps, int act, void* ws, size_t ws_bytes, void* stream) {
+    return layernorm_fwd_t<dwc_bf16>((const dwc_bf16*)x, gamma, beta, (dwc_bf16*)y, mean, inv, B, HW, C, eps, act, ws, ws_bytes,
                                      stream);
 }
 int dwc_bf16_layernorm_bwd(const void* dy, const void* x, const float* mean, const float* inv, const float* gamma,
-                           const float* beta, void* dx, float* dgamma, float* dbeta, int B, int HW, int C, float eps, int relu,
+                           const float* beta, void* dx, float* dgamma, float* dbeta, int B, int HW, int C, float eps, int act,
                            void* ws, size_t ws_bytes, void* stream) {
     return layernorm_bwd_t<dwc_bf16>((const dwc_bf16*)dy, (const dwc_bf16*)x, mean, inv, gamma, beta, (dwc_bf16*)dx, dgamma, dbeta,
-                                     B, HW, C, eps, relu, ws, ws_bytes, stream);
+                                     B, HW, C, eps, act, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

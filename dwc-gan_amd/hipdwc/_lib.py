@@ -62,6 +62,9 @@ SIGNATURES = {
     "dwc_linear_small_ok": (c_int, [c_int] * 3),
     "dwc_linear_small_fwd": (c_int, [c_fp] * 4 + [c_int] * 4 + [c_fp]),
     "dwc_linear_small_bwd": (c_int, [c_fp] * 7 + [c_int] * 3 + [c_fp]),
+    "dwc_linear_small_fwd_act": (c_int, [c_fp] * 4 + [c_int] * 4 + [c_f, c_fp]),
+    "dwc_linear_small_bwd_act": (c_int, [c_fp] * 7 + [c_int] * 4 + [c_f, c_fp]),
+    "dwc_norm_act_ok": (c_int, [c_int]),        # activation codes the norm / linear_small entry points fuse (0 / 1 / 2 = none / relu / lrelu)
     "dwc_instnorm_ws_bytes": (c_sz, [c_int, c_int, c_int]),
     "dwc_instnorm_fwd": (c_int, [c_fp] * 7 + [c_int, c_int, c_int, c_f, c_int, c_fp, c_sz, c_fp]),
     "dwc_instnorm_bwd": (c_int, [c_fp] * 9 + [c_int, c_int, c_int, c_int, c_fp, c_sz, c_fp]),
@@ -247,7 +250,12 @@ def load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)     # AttributeError if the library does not export it
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            # (e.g. a DWC_HIP_LIB build from before dwc_norm_act_ok: it would take activation code 2, lrelu, for "relu is on")
+            raise ImportError("%s does not export %s, which this binding declares (include/dwcgan_hip.h): rebuild it with "
+                              "`make -C dwc-gan_amd/csrc`" % (LIB_PATH, name)) from None
         fn.restype = res
         fn.argtypes = args
     got = lib.dwc_version()

@@ -593,6 +593,10 @@ SMALLK_X3 = int(os.environ.get("DWC_X3_SMALLK", "1"))     # fp32 7x7 weight grad
 LSTM_SEQ = int(os.environ.get("DWC_LSTM_SEQ", "1"))       # text-encoder LSTM forward: all time steps in one persistent launch
 DGRAD_FOLD = int(os.environ.get("DWC_DGRAD_FOLD", "1"))   # data gradients through a reflect pad: interior straight into dx + band fold
 X3_S2 = int(os.environ.get("DWC_X3_S2", "1"))             # fp32 stride-2 4x4 forwards as split products (csrc/conv_halo_x3.hip, S2)
+# LeakyReLU(0.1) fused into the IN / AdaIN / LN apply passes and their backward (csrc/norm.hip), as ReLU always was.  0: blocks with an
+# IN / AdaIN / LN norm and lrelu take the route from before the fused form -- the norm on its own, then torch's leaky_relu -- which is
+# the A/B partner of benchmarks/lrelu_fused_overhead.py.
+NORM_ACT_FUSED = int(os.environ.get("DWC_NORM_ACT_FUSED", "1"))
 S2HALO = int(os.environ.get("DWC_BF16_S2_HALO", "1"))     # stride-2 4x4 forwards on the halo kernel over the space-to-depth image
 S2DGRAD = int(os.environ.get("DWC_S2_DGRAD_HALO", "1"))   # stride-2 4x4 DATA GRADIENTS in halo form (interior) + ring strips, both precisions
 X3_WGRAD_HALO3 = int(os.environ.get("DWC_X3_WGRAD_HALO3", "1"))   # 0: 3x3 weight gradients on the im2col kernel (split-product inner product)
@@ -1472,25 +1476,48 @@ def max_pool2(x):
     return _MaxPool2.apply(x)
 
 
+# activation codes the norm apply passes and linear_small fuse (DWC_ACT_NONE / _RELU / _LRELU)
+NORM_ACTS = {"none": 0, "relu": 1, "lrelu": 2}
+_NORM_ACT_ASKED = set()        # codes above 1 that dwc_norm_act_ok of the loaded library has confirmed
+
+
+def norm_act_code(act, relu=False):
+    """Activation code of ``act`` ("none" / "relu" / "lrelu"; None: ``relu`` decides, the argument from before ``act``)."""
+    if act is None:
+        return 1 if relu else 0
+    if act not in NORM_ACTS:
+        raise ValueError("activation %r is not fused into the norm / linear kernels (one of %s)" % (act, sorted(NORM_ACTS)))
+    code = NORM_ACTS[act]
+    if code > 1 and code not in _NORM_ACT_ASKED:      # (codes 0 / 1 are what every build of the library has always taken)
+        if not _lib.load().dwc_norm_act_ok(code):
+            raise _lib.HipKernelError("the loaded library does not fuse activation %r (dwc_norm_act_ok(%d) == 0)" % (act, code))
+        _NORM_ACT_ASKED.add(code)
+    return code
+
+
 LINEAR_SMALL = int(os.environ.get("DWC_LINEAR_SMALL", "1"))      # nn.Linear on few rows on csrc/linear_small.hip (0: the 1x1-convolution path)
 
 
 class _LinearSmall(torch.autograd.Function):
-    """y = relu?(x w^T + b) for fp32 activations of a few rows: one launch forward, two backward (csrc/linear_small.hip; r06).  The
+    """y = act(x w^T + b), act = code 0 / 1 / 2 (none / relu / lrelu 0.1), for fp32 activations of a few rows: one launch forward, two backward (csrc/linear_small.hip; r06).  The
     weights are read as nn.Linear stores them: no prepared layout to refresh."""
 
     @staticmethod
-    def forward(ctx, x, w, b, relu):
+    def forward(ctx, x, w, b, act, slope=0.1):
         lib = _lib.load()
+        act, slope = int(act), float(slope)
         x, w = x.contiguous(), w.contiguous()
         M, K = x.shape
         N = w.shape[0]
         y = torch.empty((M, N), dtype=torch.float32, device=x.device)
-        _lib.check(_timed("linear_small_kernel", 2.0 * M * N * K, lambda: lib.dwc_linear_small_fwd(
-            x.data_ptr(), w.data_ptr(), _p(b), y.data_ptr(), M, N, K, int(relu), _stream()),
+        # (dwc_linear_small_fwd has LeakyReLU's usual slope, 0.1; the _act entry point takes any other)
+        fwd = ((lambda: lib.dwc_linear_small_fwd(x.data_ptr(), w.data_ptr(), _p(b), y.data_ptr(), M, N, K, act, _stream())) if slope == 0.1 else
+               (lambda: lib.dwc_linear_small_fwd_act(x.data_ptr(), w.data_ptr(), _p(b), y.data_ptr(), M, N, K, act, slope, _stream())))
+        _lib.check(_timed("linear_small_kernel", 2.0 * M * N * K, fwd,
             detail="fwd-lin B%d 1x1 %d>%d k1 s1" % (M, K, N)), "linear_small_fwd")
-        ctx.save_for_backward(x, w, y if relu else None)
+        ctx.save_for_backward(x, w, y if act else None)
         ctx.has_b = b is not None
+        ctx.act, ctx.slope = act, slope
         return y
 
     @staticmethod
@@ -1503,21 +1530,25 @@ class _LinearSmall(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
         db = torch.empty(N, dtype=torch.float32, device=x.device) if (ctx.has_b and ctx.needs_input_grad[2] and dw is not None) else None
-        _lib.check(_timed("linear_small_kernel", 2.0 * M * N * K * ((dx is not None) + (dw is not None)), lambda: lib.dwc_linear_small_bwd(
-            dy.data_ptr(), _p(y), x.data_ptr(), w.data_ptr(), _p(dx), _p(dw), _p(db), M, N, K, _stream()),
+        _lib.check(_timed("linear_small_kernel", 2.0 * M * N * K * ((dx is not None) + (dw is not None)), lambda: lib.dwc_linear_small_bwd_act(
+            dy.data_ptr(), _p(y), x.data_ptr(), w.data_ptr(), _p(dx), _p(dw), _p(db), M, N, K, ctx.act, ctx.slope, _stream()),
             scope_name=("bwd:" + SCOPE) if SCOPE else "", detail="bwd-lin B%d 1x1 %d>%d k1 s1" % (M, K, N)), "linear_small_bwd")
         if ctx.has_b and ctx.needs_input_grad[2] and db is None:        # (bias gradient alone: column sums of the masked dy)
-            g = dy if y is None else dy * (y > 0)
+            g = dy if y is None else (dy * (y > 0) if ctx.act == 1 else torch.where(y > 0, dy, dy * ctx.slope))
             db = g.sum(0)
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
-def linear(x, w, b, act="none", owner=None):
-    """nn.Linear (+ReLU) (reference networks.py:587-634): on csrc/linear_small.hip where the shape fits (fp32, widths multiples of 16,
-    at most 4096 rows), else as a 1x1 convolution over a 1x1 image (input width a power of two >= 4)."""
-    if (LINEAR_SMALL and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and w.dtype == torch.float32 and act in ("none", "relu", None)
+def linear(x, w, b, act="none", owner=None, slope=0.1):
+    """nn.Linear (+ReLU / LeakyReLU) (reference networks.py:587-634): on csrc/linear_small.hip where the shape fits (fp32, widths
+    multiples of 16, at most 4096 rows), else as a 1x1 convolution over a 1x1 image (input width a power of two >= 4).  ``slope``:
+    LeakyReLU's (act='lrelu'); the convolution epilogues have 0.1 only, so any other slope needs a shape linear_small takes."""
+    if (LINEAR_SMALL and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and w.dtype == torch.float32 and act in ("none", "relu", "lrelu", None)
             and _lib.load().dwc_linear_small_ok(x.shape[0], w.shape[0], x.shape[1])):
-        return _LinearSmall.apply(x, w, b, act == "relu")
+        return _LinearSmall.apply(x, w, b, norm_act_code(act), slope if act == "lrelu" else 0.1)
+    if act == "lrelu" and slope != 0.1:
+        raise NotImplementedError("linear with LeakyReLU(%g) on %d x %d -> %d %s: csrc/linear_small.hip does not take it and the "
+                                  "convolution epilogue has LeakyReLU(0.1) only" % (slope, x.shape[0], x.shape[1], w.shape[0], x.dtype))
     y = conv2d(x.reshape(x.shape[0], x.shape[1], 1, 1), w.reshape(w.shape[0], w.shape[1], 1, 1), b, 1, 0, act, owner=owner or w)
     return y.reshape(x.shape[0], -1)
 
@@ -1787,7 +1818,7 @@ def lstm_bidir(x, lens, w_ih, w_hh, b_ih, b_hh, owners=None):
 # --------------------------------------------------------------------------------------
 class _InstNorm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, residual, relu, eps, token=None):
+    def forward(ctx, x, gamma, beta, residual, act, eps, token=None):
         _require_device(x)
         ctx.token = token if residual is not None else None
         lib = _lib.load()
@@ -1805,16 +1836,16 @@ class _InstNorm(torch.autograd.Function):
         ya, yep = out_amax(y)
         if ya is not None:
             _lib.check(lib.dwc_instnorm_fwd_amax(x.data_ptr(), _p(gamma), _p(beta), _p(residual), y.data_ptr(), mean.data_ptr(),
-                                                 rstd.data_ptr(), B, H * W, C, eps, int(relu), ws.data_ptr(), ws.numel(),
+                                                 rstd.data_ptr(), B, H * W, C, eps, int(act), ws.data_ptr(), ws.numel(),
                                                  ya, yep, _stream()), "instnorm_fwd")
             set_amax(y, ya, yep)
         else:
             _lib.check(_fn(lib, "instnorm_fwd", x)(x.data_ptr(), _p(gamma), _p(beta), _p(residual), y.data_ptr(), mean.data_ptr(),
-                                                   rstd.data_ptr(), B, H * W, C, eps, int(relu), ws.data_ptr(), ws.numel(),
+                                                   rstd.data_ptr(), B, H * W, C, eps, int(act), ws.data_ptr(), ws.numel(),
                                                    _stream()), "instnorm_fwd")
         _hbm("instnorm_fwd", x.numel() * x.element_size() * (3 if residual is not None else 2))
         ctx.save_for_backward(x, mean, rstd, gamma, beta)
-        ctx.relu = int(relu)
+        ctx.act = int(act)
         ctx.has_res = residual is not None
         return y
 
@@ -1834,12 +1865,12 @@ class _InstNorm(torch.autograd.Function):
         da, dep = out_amax(dx)
         if da is not None:
             _lib.check(lib.dwc_instnorm_bwd_amax(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _p(gamma), _p(beta),
-                                                 dx.data_ptr(), _p(dgamma), _p(dbeta), B, H * W, C, ctx.relu, ws.data_ptr(),
+                                                 dx.data_ptr(), _p(dgamma), _p(dbeta), B, H * W, C, ctx.act, ws.data_ptr(),
                                                  ws.numel(), da, dep, _stream()), "instnorm_bwd")
             set_amax(dx, da, dep)
         else:
             _lib.check(_fn(lib, "instnorm_bwd", x)(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _p(gamma), _p(beta),
-                                                   dx.data_ptr(), _p(dgamma), _p(dbeta), B, H * W, C, ctx.relu, ws.data_ptr(),
+                                                   dx.data_ptr(), _p(dgamma), _p(dbeta), B, H * W, C, ctx.act, ws.data_ptr(),
                                                    ws.numel(), _stream()), "instnorm_bwd")
         _hbm("instnorm_bwd", x.numel() * x.element_size() * 3)
         if ctx.token is not None:                 # the first convolution of the block adds it in its data-gradient epilogue
@@ -1848,15 +1879,16 @@ class _InstNorm(torch.autograd.Function):
         return dx, dgamma, dbeta, (dy if ctx.has_res else None), None, None, None
 
 
-def instance_norm(x, gamma=None, beta=None, residual=None, relu=False, eps=1e-5, token=None):
-    """IN / AdaIN (+ReLU) (+residual add).  gamma/beta: flat [B*C] per-sample scale/shift or None.  ``token``: see
-    ResGradToken (the residual's gradient is handed to the block's first convolution instead of being returned)."""
-    return _InstNorm.apply(x, gamma, beta, residual, bool(relu), float(eps), token)
+def instance_norm(x, gamma=None, beta=None, residual=None, relu=False, eps=1e-5, token=None, act=None):
+    """IN / AdaIN (+activation) (+residual add).  gamma/beta: flat [B*C] per-sample scale/shift or None.  ``act``: "none" / "relu" /
+    "lrelu" (slope 0.1), fused into the apply pass; it wins over ``relu`` (the older spelling of none / relu) when given.  ``token``:
+    see ResGradToken (the residual's gradient is handed to the block's first convolution instead of being returned)."""
+    return _InstNorm.apply(x, gamma, beta, residual, norm_act_code(act, relu), float(eps), token)
 
 
 class _LayerNorm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, relu, eps):
+    def forward(ctx, x, gamma, beta, act, eps):
         _require_device(x)
         lib = _lib.load()
         x = cl(x)
@@ -1870,16 +1902,16 @@ class _LayerNorm(torch.autograd.Function):
         ya, yep = out_amax(y)
         if ya is not None:
             _lib.check(lib.dwc_layernorm_fwd_amax(x.data_ptr(), g.data_ptr(), b.data_ptr(), y.data_ptr(), mean.data_ptr(), inv.data_ptr(),
-                                                  B, H * W, C, eps, int(relu), ws.data_ptr(), ws.numel(), ya, yep, _stream()),
+                                                  B, H * W, C, eps, int(act), ws.data_ptr(), ws.numel(), ya, yep, _stream()),
                        "layernorm_fwd")
             set_amax(y, ya, yep)
         else:
             _lib.check(_fn(lib, "layernorm_fwd", x)(x.data_ptr(), g.data_ptr(), b.data_ptr(), y.data_ptr(), mean.data_ptr(),
-                                                    inv.data_ptr(), B, H * W, C, eps, int(relu), ws.data_ptr(), ws.numel(), _stream()),
+                                                    inv.data_ptr(), B, H * W, C, eps, int(act), ws.data_ptr(), ws.numel(), _stream()),
                        "layernorm_fwd")
         _hbm("layernorm_fwd", x.numel() * x.element_size() * 2)
         ctx.save_for_backward(x, mean, inv, g, b)
-        ctx.relu, ctx.eps = int(relu), eps
+        ctx.act, ctx.eps = int(act), eps
         return y
 
     @staticmethod
@@ -1897,18 +1929,19 @@ class _LayerNorm(torch.autograd.Function):
         if da is not None:
             _lib.check(lib.dwc_layernorm_bwd_amax(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), inv.data_ptr(), g.data_ptr(),
                                                   b.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), B, H * W, C,
-                                                  ctx.eps, ctx.relu, ws.data_ptr(), ws.numel(), da, dep, _stream()), "layernorm_bwd")
+                                                  ctx.eps, ctx.act, ws.data_ptr(), ws.numel(), da, dep, _stream()), "layernorm_bwd")
             set_amax(dx, da, dep)
         else:
             _lib.check(_fn(lib, "layernorm_bwd", x)(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), inv.data_ptr(), g.data_ptr(),
                                                     b.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), B, H * W, C,
-                                                    ctx.eps, ctx.relu, ws.data_ptr(), ws.numel(), _stream()), "layernorm_bwd")
+                                                    ctx.eps, ctx.act, ws.data_ptr(), ws.numel(), _stream()), "layernorm_bwd")
         _hbm("layernorm_bwd", x.numel() * x.element_size() * 3)
         return dx, dgamma, dbeta, None, None
 
 
-def layer_norm_munit(x, gamma, beta, relu=False, eps=1e-5):
-    return _LayerNorm.apply(x, gamma, beta, bool(relu), float(eps))
+def layer_norm_munit(x, gamma, beta, relu=False, eps=1e-5, act=None):
+    """MUNIT LayerNorm (+activation).  ``act``: as in instance_norm."""
+    return _LayerNorm.apply(x, gamma, beta, norm_act_code(act, relu), float(eps))
 
 
 # --------------------------------------------------------------------------------------

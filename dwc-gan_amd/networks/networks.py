@@ -19,6 +19,7 @@ from torch import nn
 from hipdwc import batchnorm, ops, spectral
 
 _CONV_ACTS = ("relu", "lrelu", "tanh", "sigmoid", "none")
+_NORM_ACTS = ("relu", "lrelu", "none")          # fused into the IN / AdaIN / LN apply pass and its backward (csrc/norm.hip)
 
 
 # --------------------------------------------------------------------------------------
@@ -37,10 +38,10 @@ class AdaptiveInstanceNorm2d(nn.Module):
         self.register_buffer("running_mean", torch.zeros(num_features))
         self.register_buffer("running_var", torch.ones(num_features))
 
-    def forward(self, x, relu=False, residual=None, token=None):
+    def forward(self, x, relu=False, residual=None, token=None, act=None):
         if self.weight is None or self.bias is None:
             raise AssertionError("Please assign weight and bias before calling AdaIN!")
-        return ops.instance_norm(x, self.weight, self.bias, residual=residual, relu=relu, eps=self.eps, token=token)
+        return ops.instance_norm(x, self.weight, self.bias, residual=residual, relu=relu, eps=self.eps, token=token, act=act)
 
     def __repr__(self):
         return "%s(%d)" % (type(self).__name__, self.num_features)
@@ -57,18 +58,18 @@ class LayerNorm(nn.Module):
             self.gamma = nn.Parameter(torch.Tensor(num_features).uniform_())
             self.beta = nn.Parameter(torch.zeros(num_features))
 
-    def forward(self, x, relu=False):
+    def forward(self, x, relu=False, act=None):
         if not self.affine:
             one = torch.ones(self.num_features, device=x.device)
-            return ops.layer_norm_munit(x, one, torch.zeros_like(one), relu=relu, eps=self.eps)
-        return ops.layer_norm_munit(x, self.gamma, self.beta, relu=relu, eps=self.eps)
+            return ops.layer_norm_munit(x, one, torch.zeros_like(one), relu=relu, eps=self.eps, act=act)
+        return ops.layer_norm_munit(x, self.gamma, self.beta, relu=relu, eps=self.eps, act=act)
 
 
 class _PlainInstanceNorm(nn.InstanceNorm2d):
     """nn.InstanceNorm2d(affine=False) as a marker/parameter-less container (reference networks.py:545)."""
 
-    def forward(self, x, relu=False, residual=None, token=None):
-        return ops.instance_norm(x, None, None, residual=residual, relu=relu, eps=self.eps, token=token)
+    def forward(self, x, relu=False, residual=None, token=None, act=None):
+        return ops.instance_norm(x, None, None, residual=residual, relu=relu, eps=self.eps, token=token, act=act)
 
 
 class SegmentedBatchNorm2d(nn.BatchNorm2d):
@@ -122,11 +123,13 @@ class Conv2dBlock(nn.Module):
     """pad -> conv -> norm -> activation (reference networks.py:524-585) as at most two fused passes.
 
     What the shipped configurations use -- reflect padding, norm in {none, in, ln, adain}, activation in {relu, lrelu, tanh, sigmoid,
-    none} -- is all HIP: the padding rule inside the convolution's gather, bias / activation in its epilogue, ReLU and the residual
-    add in the norm's apply pass.  The rest of the reference's signature is reachable too (r05), through stock PyTorch-ROCm DEVICE
-    ops around the HIP convolution: ``pad_type`` zero / replicate at stride 1 (``F.pad``, then the convolution without padding),
-    ``activation`` prelu / selu (``nn.PReLU`` / ``F.selu``), and any norm followed by an activation other than
-    ReLU (the norm unfused, then the activation).  ``norm='bn'`` is SegmentedBatchNorm2d on the HIP kernels with none / relu / lrelu
+    none} -- is all HIP: the padding rule inside the convolution's gather, bias / activation in its epilogue, ReLU / LeakyReLU(0.1)
+    and the residual add in the norm's apply pass (``dis.norm: in / ln`` with the default ``dis.activ: lrelu``, ``gen.activ: lrelu``;
+    hipdwc.ops.NORM_ACT_FUSED = 0 puts lrelu back behind the unfused norm).  The rest of the reference's signature is reachable too
+    (r05), through stock PyTorch-ROCm DEVICE ops around the HIP convolution: ``pad_type`` zero / replicate at stride 1 (``F.pad``, then
+    the convolution without padding), ``activation`` prelu / selu (``nn.PReLU`` / ``F.selu``), and an in / ln / adain norm followed by
+    an activation other than ReLU / LeakyReLU (tanh / sigmoid / prelu / selu: the norm unfused, then the activation).  ``norm='bn'``
+    is SegmentedBatchNorm2d on the HIP kernels with none / relu / lrelu
     fused (``segments`` / ``stat_order``: the batch is S equal segments, each with its own batch statistics, the running buffers
     stepped in ``stat_order``; hipdwc.batchnorm).  ``norm='sn'`` wraps the convolution in SpectralNorm like the reference: one power
     iteration per call (``segments`` = S: the batch is S equal segments and segment s uses the s-th of S consecutive iterations), the
@@ -212,19 +215,18 @@ class Conv2dBlock(nn.Module):
             if not fused:
                 y = self._torch_act(y)
             return y if residual is None else y + residual
-        if self.act_kind not in ("relu", "none"):
-            # off the shipped configurations: the norm on its own, then the activation
+        if self.act_kind not in (_NORM_ACTS if ops.NORM_ACT_FUSED else ("relu", "none")):
+            # prelu / selu / tanh / sigmoid (and lrelu with DWC_NORM_ACT_FUSED=0): the norm on its own, then the activation
             y = ops.conv2d(x, self.conv.weight, self.conv.bias, self.stride, pad, "none", token=conv_token)
             y = self.norm(y) if self.norm_kind == "ln" else self.norm(y, relu=False)
             y = torch.relu(y) if self.act_kind == "relu" else (y if self.act_kind == "none" else self._torch_act(y))
             return y if residual is None else y + residual
         y = ops.conv2d(x, self.conv.weight, self.conv.bias, self.stride, pad, "none",
                        bias_grad=self.norm_kind == "ln", token=conv_token)   # IN / AdaIN subtract the per-(n,c) mean: d/d bias == 0
-        relu = self.act_kind == "relu"
         if self.norm_kind == "ln":
-            y = self.norm(y, relu=relu)
+            y = self.norm(y, act=self.act_kind)
             return y if residual is None else y + residual
-        return self.norm(y, relu=relu, residual=residual, token=res_token)
+        return self.norm(y, act=self.act_kind, residual=residual, token=res_token)
 
 
 class ResBlock(nn.Module):
@@ -253,10 +255,11 @@ class ResBlock(nn.Module):
         torch.cat([x] * groups) up to fp32 summation order (the three groups' gradients meet before the convolution instead of
         inside its batch)."""
         c0, c1 = self.model[0], self.model[1]
-        if c0.norm_kind != "adain" or c0.act_kind != "relu" or c0.pad_type != "reflect" or c1.norm_kind != "adain":
+        acts = ("relu", "lrelu") if ops.NORM_ACT_FUSED else ("relu",)
+        if c0.norm_kind != "adain" or c0.act_kind not in acts or c0.pad_type != "reflect" or c1.norm_kind != "adain":
             return self.forward(torch.cat([x] * groups), 1)
         y = ops.conv2d(x, c0.conv.weight, c0.conv.bias, c0.stride, c0.padding, "none", bias_grad=False)
-        h = c0.norm(torch.cat([y] * groups), relu=True)
+        h = c0.norm(torch.cat([y] * groups), act=c0.act_kind)
         return c1(h, residual=torch.cat([x] * groups))
 
 
@@ -276,20 +279,23 @@ class ResBlocks(nn.Module):
 
 
 class LinearBlock(nn.Module):
-    """Linear (+ReLU) (reference networks.py:587-634) on the 1x1-conv kernel."""
+    """Linear (+ReLU / LeakyReLU) (reference networks.py:587-634) on csrc/linear_small.hip, or the 1x1-conv kernel where the shape does
+    not fit it.  The reference's LinearBlock has LeakyReLU(0.2) (networks.py:614) where its Conv2dBlock has 0.1 (networks.py:559)."""
+
+    LRELU_SLOPE = 0.2
 
     def __init__(self, input_dim, output_dim, norm="none", activation="relu"):
         super().__init__()
         if norm != "none":
             raise NotImplementedError("LinearBlock norm %r is not on the HIP path" % norm)
-        if activation not in ("relu", "none"):
+        if activation not in ("relu", "lrelu", "none"):
             raise NotImplementedError("LinearBlock activation %r is not on the HIP path" % activation)
         self.act_kind = activation
         self.norm = None
         self.fc = nn.Linear(input_dim, output_dim, bias=True)
 
     def forward(self, x):
-        return ops.linear(x, self.fc.weight, self.fc.bias, self.act_kind)
+        return ops.linear(x, self.fc.weight, self.fc.bias, self.act_kind, slope=self.LRELU_SLOPE)
 
 
 class MLP(nn.Module):

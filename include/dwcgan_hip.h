@@ -146,11 +146,17 @@ int dwc_act_bwd_bias(const float* dy, const float* y, float* g, float* db, int r
 
 /* ---- instance norm / AdaIN (reference networks.py:545 nn.InstanceNorm2d and
  *      networks.py:706-719 AdaptiveInstanceNorm2d; residual add networks.py:518-522) --------- */
-/* y = relu?( (x-mean[n,c])*rstd[n,c]*gamma[n,c] + beta[n,c] ) + residual?
+/* y = act( (x-mean[n,c])*rstd[n,c]*gamma[n,c] + beta[n,c] ) + residual?
  * gamma/beta: [B*C] or NULL (plain IN).  mean/rstd [B*C] are outputs kept for the backward.
+ * `relu` of every instance-norm / layer-norm entry point (fp32, *_amax, dwc_bf16_*) and of dwc_linear_small_fwd is an ACTIVATION CODE:
+ * 0 = DWC_ACT_NONE and 1 = DWC_ACT_RELU as ever, 2 = DWC_ACT_LRELU (t < 0 ? 0.1 t : t); anything else returns DWC_EINVAL before any
+ * launch.  The backward takes the slope from the sign of the pre-activation, recomputed with the forward's expression and rounding
+ * (not from x-hat: AdaIN's gamma may be negative).  dwc_norm_act_ok(act) = 1 for the codes this build fuses: host only, no launch; a
+ * binding asks it before it passes a code other than 0 / 1 (a build without the symbol knows 0 / 1 only).
  * (ABI 8 dropped the `tickets` argument of the six instance-norm entry points and the ticket-row size query: rounds 3-4 finalised
  * the statistics inside the partial launch through a caller-owned ticket row; measured at batch 16 that cost 3-5x what a parallel
  * finalise launch costs (csrc/norm.hip), so the statistics are finalised by their own small launch.)  The library keeps no mutable state. */
+int dwc_norm_act_ok(int act);
 size_t dwc_instnorm_ws_bytes(int B, int HW, int C);
 int dwc_instnorm_fwd(const float* x, const float* gamma, const float* beta, const float* residual,
                      float* y, float* mean, float* rstd, int B, int HW, int C, float eps, int relu,
@@ -160,17 +166,25 @@ int dwc_instnorm_bwd(const float* dy, const float* x, const float* mean, const f
                      const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta,
                      int B, int HW, int C, int relu, void* ws, size_t ws_bytes, void* stream);
 
-/* ---- nn.Linear (+ ReLU) on few rows (r06, ABI 8): the style -> AdaIN-parameter MLP (reference networks.py:491-503, LinearBlock
+/* ---- nn.Linear (+ ReLU / LeakyReLU) on few rows (r06, ABI 8): the style -> AdaIN-parameter MLP (reference networks.py:491-503, LinearBlock
  *      :587-634) and the style encoder's mapping (networks_v2.py:116-121) ------------------------------------------------------
- * y[M][N] = act(x[M][K] . w[N][K]^T + bias[N]), fp32 row-major, w as nn.Linear stores it (no prepared layout); relu != 0: ReLU.
+ * y[M][N] = act(x[M][K] . w[N][K]^T + bias[N]), fp32 row-major, w as nn.Linear stores it (no prepared layout); relu = activation
+ * code 0 / 1 / 2 (none / ReLU / LeakyReLU 0.1, see dwc_instnorm_fwd).
  * One wave per 16 x 16 output tile on the exact fp32 matrix instruction (v_mfma_f32_16x16x4_f32), operands straight from memory: no
  * LDS, no scratch.  _ok: N and K multiples of 16, M <= 4096 (larger problems belong on dwc_conv2d_fwd as a 1x1 convolution).
  * dwc_linear_small_bwd: dx[M][K] (NULL: skipped), dw[N][K] and db[N] (NULL: skipped) from dy[M][N]; y_relu = the forward's output when
- * it had the ReLU (the mask is applied while dy is read), else NULL. */
+ * it had the ReLU (the mask is applied while dy is read), else NULL.
+ * dwc_linear_small_fwd_act / _bwd_act: the same with an activation code and LeakyReLU's slope (used when act == 2; in (0, 1), else
+ * DWC_EINVAL: the reference's LinearBlock has 0.2, networks.py:614, its Conv2dBlock 0.1); y_act = the forward's output (required
+ * unless act == 0): g = y > 0 ? dy : slope * dy, read off the output, which keeps the sign of the pre-activation. */
 int dwc_linear_small_ok(int M, int N, int K);
 int dwc_linear_small_fwd(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int relu, void* stream);
 int dwc_linear_small_bwd(const float* dy, const float* y_relu, const float* x, const float* w, float* dx, float* dw, float* db, int M,
                          int N, int K, void* stream);
+int dwc_linear_small_fwd_act(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int act, float slope,
+                             void* stream);
+int dwc_linear_small_bwd_act(const float* dy, const float* y_act, const float* x, const float* w, float* dx, float* dw, float* db,
+                             int M, int N, int K, int act, float slope, void* stream);
 
 /* ---- MUNIT LayerNorm (reference networks.py:736-752: per-sample mean, UNBIASED std,
  *      (x-mean)/(std+eps), per-channel gamma/beta) ------------------------------------------ */
