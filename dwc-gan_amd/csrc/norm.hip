@@ -15,8 +15,6 @@
 // order (bitwise reproducible; no atomics).
 #include <stdlib.h>
 
-#include <atomic>
-
 #include <type_traits>
 
 #include "dwc_common.h"
@@ -84,9 +82,45 @@ RowSplit plan_apply(int B, int HW, int C, int V) {
     return r;
 }
 
+// Thread geometry of the row-walking kernels (the *_partial and *_apply kernels of all three norms): a 256-thread block is `groups` row
+// groups x `cq` column groups of V channels, thread (rg, col) takes rows r0 + rg, r0 + rg + groups, ... of its column group.
+// INVARIANT: groups * cq == 256 for a power-of-two C (IN, LN); batch norm takes any multiple of V, and then the threads with
+// rg >= groups walk no rows but reach every barrier behind the walk: the LDS sum of colsum_groups in the *_partial kernels, the
+// absmax publish of the *_apply kernels.
+// (The walks themselves stay written out in the ten kernels.  As function templates taking the per-row functor they compiled to other
+// code: the accumulate walk contracted other products of ln_bwd_partial<float, relu> into FMAs -- dgamma and dx of layer norm changed
+// bits -- and the apply walk cost ln_apply<float> 0.7 us of 32 per launch inside the benchmark step: profiles/norm_refactor.txt.)
+template <int V> struct RowGeom {
+    int cq, groups, col, rg;
+    __device__ __forceinline__ explicit RowGeom(int C) : cq(C / V), groups(256 / cq), col(threadIdx.x % cq), rg(threadIdx.x / cq) {}
+};
+
+// a += p[i * stride], b += p[second + i * stride] for i = first, first + step, ... < count, U pairs in flight, added in index order
+// (fixed order: bitwise reproducible)
+template <int U>
+__device__ __forceinline__ void strided_sum2(const float* __restrict__ p, size_t second, size_t stride, int first, int step, int count,
+                                             float& a, float& b) {
+    int k = first;
+    for (; k + (U - 1) * step < count; k += U * step) {
+        float va[U], vb[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            va[u] = p[(size_t)(k + step * u) * stride];
+            vb[u] = p[second + (size_t)(k + step * u) * stride];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) a += va[u], b += vb[u];
+    }
+    for (; k < count; k += step) {
+        a += p[(size_t)k * stride];
+        b += p[second + (size_t)k * stride];
+    }
+}
+
 // sum of `groups` row-group partials held in LDS (fixed order: bitwise reproducible), for the thread with rg == 0
 template <int V>
-__device__ __forceinline__ void colsum_groups(float (&a)[V], float (&b)[V], float* sm, int groups, int cq, int col, int rg) {
+__device__ __forceinline__ void colsum_groups(float (&a)[V], float (&b)[V], float* sm, const RowGeom<V>& geo) {
+    const int groups = geo.groups, cq = geo.cq, col = geo.col, rg = geo.rg;
     // layout sm[plane][t][V] with t = rg * cq + col
     float* s0 = sm;
     float* s1 = sm + 256 * V;
@@ -122,9 +156,8 @@ __global__ __launch_bounds__(256) void in_stats_partial(const T* __restrict__ x,
                                                         int rows_per_chunk, size_t plane) {
     constexpr int V = VecOf<T>::V;
     __shared__ float sm[2 * 256 * V];
-    const int cq = C / V;
-    const int groups = 256 / cq;
-    const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
+    const RowGeom<V> geo(C);
+    const int cq = geo.cq, groups = geo.groups, col = geo.col, rg = geo.rg;
     const int n = blockIdx.y, chunk = blockIdx.x;
     const T* xs = x + (size_t)n * HW * C;
     float piv[V];
@@ -160,7 +193,7 @@ __global__ __launch_bounds__(256) void in_stats_partial(const T* __restrict__ x,
             }
         }
     }
-    colsum_groups<V>(s1, s2, sm, groups, cq, col, rg);
+    colsum_groups<V>(s1, s2, sm, geo);
     if (rg == 0) {
         const size_t o = ((size_t)(n * gridDim.x + chunk) * C) + col * V;
         stf<V>(part, o, s1);
@@ -168,44 +201,35 @@ __global__ __launch_bounds__(256) void in_stats_partial(const T* __restrict__ x,
     }
 }
 
-// Sum of the per-chunk partials of one (sample, channel): 64 channels x 4 chunk lanes per workgroup, chunk lane q takes chunks q, q + 4, ...
-// with eight loads per plane in flight, the four lane sums are added in lane order (fixed order: bitwise reproducible).  r05: the
-// one-thread-per-channel loops of in_stats_final / in_bwd_final took 17-33 us at batch 16 (64-128 chunks, one dependent load after
-// the other), and the fused finalisation in the last-arriving workgroup of a sample 20-60 us more than that (2 048 agent-scope
-// acquire/release tickets per launch): in_stats_partial 71.9 us fused against 12.6 + 33.1 unfused at 16 x 128 x 128 x 64.
-__device__ __forceinline__ void norm_chunk_lanes(const float* __restrict__ p, size_t plane, int C, int chunks, int q, float& a, float& b) {
-    int k = q;
-    for (; k + 28 < chunks; k += 32) {
-        float va[8], vb[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            va[u] = p[(size_t)(k + 4 * u) * C];
-            vb[u] = p[plane + (size_t)(k + 4 * u) * C];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) a += va[u], b += vb[u];
-    }
-    for (; k < chunks; k += 4) {
-        a += p[(size_t)k * C];
-        b += p[plane + (size_t)k * C];
-    }
-}
-
-// grid (ceil(C / 64), B), 256 threads
-template <typename T>
-__global__ __launch_bounds__(256) void in_stats_final_wide(const T* __restrict__ x, const float* __restrict__ part, float* __restrict__ mean,
-                                                           float* __restrict__ rstd, int HW, int C, int chunks, size_t plane, float eps) {
+// The front of both *_final_wide kernels (grid (ceil(C / 64), B), 256 threads): the sum of the per-chunk partials of (sample
+// n = blockIdx.y, channel c).  64 channels x 4 chunk lanes per workgroup, chunk lane q takes chunks q, q + 4, ... with eight loads per
+// plane in flight, the four lane sums go through LDS and are added in lane order (fixed order: bitwise reproducible).  True for the one
+// thread of the channel that holds s1, s2; false for the other lanes and the channels past C.  r05: the one-thread-per-channel loops
+// of in_stats_final / in_bwd_final took 17-33 us at batch 16 (64-128 chunks, one dependent load after the other), and the fused
+// finalisation in the last-arriving workgroup of a sample 20-60 us more than that (2 048 agent-scope acquire/release tickets per
+// launch): in_stats_partial 71.9 us fused against 12.6 + 33.1 unfused at 16 x 128 x 128 x 64.
+__device__ __forceinline__ bool norm_chunk_sums(const float* __restrict__ part, size_t plane, int C, int chunks, int& c, float& s1, float& s2) {
     __shared__ float sm[2][4][64];
     const int n = blockIdx.y, cl = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
+    c = blockIdx.x * 64 + cl;
     float a = 0.f, b = 0.f;
-    if (c < C) norm_chunk_lanes(part + (size_t)n * chunks * C + c, plane, C, chunks, q, a, b);
+    if (c < C) strided_sum2<8>(part + (size_t)n * chunks * C + c, plane, C, q, 4, chunks, a, b);
     sm[0][q][cl] = a;
     sm[1][q][cl] = b;
     __syncthreads();
-    if (q != 0 || c >= C) return;
-    const float s1 = ((sm[0][0][cl] + sm[0][1][cl]) + sm[0][2][cl]) + sm[0][3][cl];
-    const float s2 = ((sm[1][0][cl] + sm[1][1][cl]) + sm[1][2][cl]) + sm[1][3][cl];
+    if (q != 0 || c >= C) return false;
+    s1 = ((sm[0][0][cl] + sm[0][1][cl]) + sm[0][2][cl]) + sm[0][3][cl];
+    s2 = ((sm[1][0][cl] + sm[1][1][cl]) + sm[1][2][cl]) + sm[1][3][cl];
+    return true;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void in_stats_final_wide(const T* __restrict__ x, const float* __restrict__ part, float* __restrict__ mean,
+                                                           float* __restrict__ rstd, int HW, int C, int chunks, size_t plane, float eps) {
+    const int n = blockIdx.y;
+    int c;
+    float s1, s2;
+    if (!norm_chunk_sums(part, plane, C, chunks, c, s1, s2)) return;
     const float inv = 1.f / (float)HW;
     const float d = s1 * inv;
     const float var = fmaxf(s2 * inv - d * d, 0.f);
@@ -215,17 +239,10 @@ __global__ __launch_bounds__(256) void in_stats_final_wide(const T* __restrict__
 
 __global__ __launch_bounds__(256) void in_bwd_final_wide(const float* __restrict__ part, float* __restrict__ sums, float* __restrict__ dgamma,
                                                          float* __restrict__ dbeta, int BC, int C, int chunks, size_t plane) {
-    __shared__ float sm[2][4][64];
-    const int n = blockIdx.y, cl = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    float a = 0.f, b = 0.f;
-    if (c < C) norm_chunk_lanes(part + (size_t)n * chunks * C + c, plane, C, chunks, q, a, b);
-    sm[0][q][cl] = a;
-    sm[1][q][cl] = b;
-    __syncthreads();
-    if (q != 0 || c >= C) return;
-    const float s1 = ((sm[0][0][cl] + sm[0][1][cl]) + sm[0][2][cl]) + sm[0][3][cl];
-    const float s2 = ((sm[1][0][cl] + sm[1][1][cl]) + sm[1][2][cl]) + sm[1][3][cl];
+    const int n = blockIdx.y;
+    int c;
+    float s1, s2;
+    if (!norm_chunk_sums(part, plane, C, chunks, c, s1, s2)) return;
     const size_t idx = (size_t)n * C + c;
     sums[idx] = s1;
     sums[BC + idx] = s2;
@@ -241,10 +258,8 @@ __global__ __launch_bounds__(256) void in_apply(const T* __restrict__ x, const f
                                                 unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
     constexpr int V = VecOf<T>::V;
     const float slope = dwc_act_slope(act);
-    const int cq = C / V;
-    const int groups = 256 / cq;
-    const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
-    // (threads past the last row group -- none while groups * cq == 256 -- walk no rows below but still reach the publish barrier)
+    const RowGeom<V> geo(C);
+    const int cq = geo.cq, groups = geo.groups, col = geo.col, rg = geo.rg;
     unsigned am = 0;                                       // largest |y| this thread writes (two-plane conv kernels: absmax slot of y)
     const int n = blockIdx.y;
     const size_t s = (size_t)n * C + col * V;
@@ -309,9 +324,8 @@ __global__ __launch_bounds__(256) void in_bwd_partial(const T* __restrict__ dy, 
                                                       int act) {
     constexpr int V = VecOf<T>::V;
     __shared__ float sm[2 * 256 * V];
-    const int cq = C / V;
-    const int groups = 256 / cq;
-    const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
+    const RowGeom<V> geo(C);
+    const int cq = geo.cq, groups = geo.groups, col = geo.col, rg = geo.rg;
     const int n = blockIdx.y, chunk = blockIdx.x;
     const size_t base = (size_t)n * HW * cq + col;
     const size_t s = (size_t)n * C + col * V;
@@ -358,7 +372,7 @@ __global__ __launch_bounds__(256) void in_bwd_partial(const T* __restrict__ dy, 
             acc(x0, d0);
         }
     }
-    colsum_groups<V>(s1, s2, sm, groups, cq, col, rg);
+    colsum_groups<V>(s1, s2, sm, geo);
     if (rg == 0) {
         const size_t o = ((size_t)(n * gridDim.x + chunk) * C) + col * V;
         stf<V>(part, o, s1);
@@ -374,10 +388,8 @@ __global__ __launch_bounds__(256) void in_bwd_apply(const T* __restrict__ dy, co
                                                     int rows_per_chunk, int act, unsigned long long* amax = nullptr,
                                                     unsigned amax_ep = 0) {
     constexpr int V = VecOf<T>::V;
-    const int cq = C / V;
-    const int groups = 256 / cq;
-    const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
-    // (threads past the last row group -- none while groups * cq == 256 -- walk no rows below but still reach the publish barrier)
+    const RowGeom<V> geo(C);
+    const int cq = geo.cq, groups = geo.groups, col = geo.col, rg = geo.rg;
     unsigned am = 0;
     const int n = blockIdx.y;
     const size_t s = (size_t)n * C + col * V;
@@ -518,10 +530,8 @@ __global__ __launch_bounds__(256) void ln_apply(const T* __restrict__ x, const f
                                                 const float* __restrict__ beta, T* __restrict__ y, int HW, int C, int rows_per_chunk,
                                                 int act, unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
     constexpr int V = VecOf<T>::V;
-    const int cq = C / V;
-    const int groups = 256 / cq;
-    const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
-    // (threads past the last row group -- none while groups * cq == 256 -- walk no rows below but still reach the publish barrier)
+    const RowGeom<V> geo(C);
+    const int cq = geo.cq, groups = geo.groups, col = geo.col, rg = geo.rg;
     unsigned am = 0;
     const int n = blockIdx.y;
     const float mu = mean[n], iv = inv[n];
@@ -575,9 +585,8 @@ __global__ __launch_bounds__(256) void ln_bwd_partial(const T* __restrict__ dy, 
     constexpr int V = VecOf<T>::V;
     __shared__ float sm[2 * 256 * V];
     __shared__ float sr[4];
-    const int cq = C / V;
-    const int groups = 256 / cq;
-    const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
+    const RowGeom<V> geo(C);
+    const int cq = geo.cq, groups = geo.groups, col = geo.col, rg = geo.rg;
     const int n = blockIdx.y, chunk = blockIdx.x;
     const size_t base = (size_t)n * HW * cq + col;
     const float mu = mean[n], iv = inv[n];
@@ -626,7 +635,7 @@ __global__ __launch_bounds__(256) void ln_bwd_partial(const T* __restrict__ dy, 
             acc(x0, d0);
         }
     }
-    colsum_groups<V>(dg, db, sm, groups, cq, col, rg);
+    colsum_groups<V>(dg, db, sm, geo);
     const size_t blk = (size_t)n * gridDim.x + chunk;
     if (rg == 0) {
         stf<V>(part_c, blk * 2 * C + col * V, dg);
@@ -675,22 +684,7 @@ __global__ __launch_bounds__(1024) void ln_bwd_final(const float* __restrict__ p
     float a = 0.f, b = 0.f;
     if (c < C) {
         // (r05: eight loads per sum in flight -- the plain loop was 126 dependent loads at batch 48, 35-47 us per launch)
-        const int total = B * chunks;
-        int k = g;
-        for (; k + 7 * 16 < total; k += 8 * 16) {
-            float va[8], vb[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                va[u] = part_c[(size_t)(k + 16 * u) * 2 * C + c];
-                vb[u] = part_c[(size_t)(k + 16 * u) * 2 * C + C + c];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) a += va[u], b += vb[u];
-        }
-        for (; k < total; k += 16) {
-            a += part_c[(size_t)k * 2 * C + c];
-            b += part_c[(size_t)k * 2 * C + C + c];
-        }
+        strided_sum2<8>(part_c + c, C, (size_t)2 * C, g, 16, B * chunks, a, b);
     }
     sm[0][g][cl] = a;
     sm[1][g][cl] = b;
@@ -714,10 +708,8 @@ __global__ __launch_bounds__(256, LRELU && sizeof(T) == 4 ? 7 : 1) void ln_bwd_a
                                                     int rows_per_chunk, float eps, int act, unsigned long long* amax = nullptr,
                                                     unsigned amax_ep = 0) {
     constexpr int V = VecOf<T>::V;
-    const int cq = C / V;
-    const int groups = 256 / cq;
-    const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
-    // (threads past the last row group -- none while groups * cq == 256 -- walk no rows below but still reach the publish barrier)
+    const RowGeom<V> geo(C);
+    const int cq = geo.cq, groups = geo.groups, col = geo.col, rg = geo.rg;
     unsigned am = 0;
     const int n = blockIdx.y;
     const float N = (float)HW * (float)C;
@@ -774,10 +766,6 @@ bool norm_shape_ok(int B, int HW, int C, int V) {      // C a power of two with 
     const int l = dwc_ilog2_exact(C);
     return B > 0 && HW > 0 && l >= 2 && C >= V && C <= 1024;
 }
-
-}  // namespace
-
-namespace {
 
 // ---------------------------------------------------------------------------------------
 // Resident-plane instance norm (r04): ONE pass over HBM per direction for the small planes (HW = 256 / 1024: every ResBlock
@@ -1058,21 +1046,36 @@ int in_resident_hw(int HW, int C) {
     return (HW == 1024 || HW == 256) ? HW : 0;
 }
 
-// The caller's ticket row for one statistics launch, or null when the batch is too large for the fused finalisation to pay
-// (measured r03: worth it at small batches -- c1, B = 16..48: 0.80 -> 0.71 ms and 0.86 -> 0.79 ms of statistics kernels per step plus
-// 92 launch boundaries; at B >= 128 the per-workgroup publish + ticket costs more than the *_final launch it saves).
-
-size_t instnorm_ws_bytes(int B, int HW, int C) {
-    const RowSplit rs = plan_rows(B, HW);
-    return ((size_t)2 * B * rs.chunks * C + (size_t)2 * B * C) * sizeof(float);
-}
+// Caller scratch of each norm, in floats from the start of the workspace: the ONE place that says where its regions lie.  *_ws_bytes
+// answers `bytes`, the forward and backward launchers take the row split, the plane size and their pointers from the same object.
+struct InstNormScratch {       // [2 planes of per-chunk partials][2 planes of per-(n, c) sums]
+    RowSplit rs;
+    size_t plane, sums, bytes;
+    InstNormScratch(int B, int HW, int C)
+        : rs(plan_rows(B, HW)), plane((size_t)B * rs.chunks * C), sums(2 * plane), bytes((sums + (size_t)2 * B * C) * sizeof(float)) {}
+};
+struct LayerNormScratch {      // [per-chunk sample pairs][per-chunk (dgamma, dbeta) rows of 2 C][per-sample sum pairs][16 spare]
+    RowSplit rs;
+    size_t part_c, sums, bytes;
+    LayerNormScratch(int B, int HW, int C)
+        : rs(plan_rows(B, HW)), part_c((size_t)B * rs.chunks * 2), sums(part_c + (size_t)B * rs.chunks * 2 * C),
+          bytes((sums + (size_t)2 * B + 16) * sizeof(float)) {}
+};
+struct BatchNormScratch {      // [2 planes of per-chunk partials][2 planes of per-(segment, channel) sums][16 spare]; rows split by the
+    RowSplit rs;               // SEGMENT's batch (see the batch-norm section)
+    size_t plane, sums, bytes;
+    BatchNormScratch(int S, int Bs, int HW, int C)
+        : rs(plan_rows(Bs, HW)), plane((size_t)S * Bs * rs.chunks * C), sums(2 * plane),
+          bytes((sums + (size_t)2 * S * C + 16) * sizeof(float)) {}
+};
 
 template <typename T>
 int instnorm_fwd_t(const T* x, const float* gamma, const float* beta, const T* residual, T* y, float* mean,
                      float* rstd, int B, int HW, int C, float eps, int act, void* ws, size_t ws_bytes, void* stream,
                      unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
     if (!norm_shape_ok(B, HW, C, VecOf<T>::V) || !norm_act_ok(act)) return DWC_EINVAL;
-    if (!ws || ws_bytes < instnorm_ws_bytes(B, HW, C)) return DWC_EWORKSPACE;
+    const InstNormScratch sc(B, HW, C);
+    if (!ws || ws_bytes < sc.bytes) return DWC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (const int rhw = in_resident_hw<T>(HW, C)) {          // small planes: one pass, plane resident in registers
         const int pairs = B * (C / (Raw4<T>::CQ * 4)) / 2;
@@ -1089,12 +1092,10 @@ int instnorm_fwd_t(const T* x, const float* gamma, const float* beta, const T* r
         DWC_LAUNCH_CHECK();
         return DWC_OK;
     }
-    const RowSplit rs = plan_rows(B, HW);
-    const size_t plane = (size_t)B * rs.chunks * C;
     float* part = (float*)ws;
-    hipLaunchKernelGGL(in_stats_partial<T>, dim3(rs.chunks, B), dim3(256), 0, st, x, part, HW, C, rs.rows_per_chunk, plane);
+    hipLaunchKernelGGL(in_stats_partial<T>, dim3(sc.rs.chunks, B), dim3(256), 0, st, x, part, HW, C, sc.rs.rows_per_chunk, sc.plane);
     DWC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(in_stats_final_wide<T>, dim3((C + 63) / 64, B), dim3(256), 0, st, x, part, mean, rstd, HW, C, rs.chunks, plane, eps);
+    hipLaunchKernelGGL(in_stats_final_wide<T>, dim3((C + 63) / 64, B), dim3(256), 0, st, x, part, mean, rstd, HW, C, sc.rs.chunks, sc.plane, eps);
     DWC_LAUNCH_CHECK();
     const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
     hipLaunchKernelGGL(in_apply<T>, dim3(ra.chunks, B), dim3(256), 0, st, x, mean, rstd, gamma, beta, residual, y, HW, C,
@@ -1108,7 +1109,8 @@ int instnorm_bwd_t(const T* dy, const T* x, const float* mean, const float* rstd
                    const float* beta, T* dx, float* dgamma, float* dbeta, int B, int HW, int C, int act, void* ws,
                      size_t ws_bytes, void* stream, unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
     if (!norm_shape_ok(B, HW, C, VecOf<T>::V) || !norm_act_ok(act)) return DWC_EINVAL;
-    if (!ws || ws_bytes < instnorm_ws_bytes(B, HW, C)) return DWC_EWORKSPACE;
+    const InstNormScratch sc(B, HW, C);
+    if (!ws || ws_bytes < sc.bytes) return DWC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (const int rhw = in_resident_hw<T>(HW, C)) {
         const int pairs = B * (C / (Raw4<T>::CQ * 4)) / 2;
@@ -1123,14 +1125,12 @@ int instnorm_bwd_t(const T* dy, const T* x, const float* mean, const float* rstd
         DWC_LAUNCH_CHECK();
         return DWC_OK;
     }
-    const RowSplit rs = plan_rows(B, HW);
-    const size_t plane = (size_t)B * rs.chunks * C;
     float* part = (float*)ws;
-    float* sums = part + 2 * plane;
-    NORM_LAUNCH_ACT(act, in_bwd_partial, (T), dim3(rs.chunks, B), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, part, HW, C,
-                    rs.rows_per_chunk, plane, act);
+    float* sums = part + sc.sums;
+    NORM_LAUNCH_ACT(act, in_bwd_partial, (T), dim3(sc.rs.chunks, B), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, part, HW, C,
+                    sc.rs.rows_per_chunk, sc.plane, act);
     DWC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(in_bwd_final_wide, dim3((C + 63) / 64, B), dim3(256), 0, st, part, sums, dgamma, dbeta, B * C, C, rs.chunks, plane);
+    hipLaunchKernelGGL(in_bwd_final_wide, dim3((C + 63) / 64, B), dim3(256), 0, st, part, sums, dgamma, dbeta, B * C, C, sc.rs.chunks, sc.plane);
     DWC_LAUNCH_CHECK();
     const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
     NORM_LAUNCH_ACT(act, in_bwd_apply, (T), dim3(ra.chunks, B), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, sums, dx, HW, C,
@@ -1139,23 +1139,18 @@ int instnorm_bwd_t(const T* dy, const T* x, const float* mean, const float* rstd
     return DWC_OK;
 }
 
-size_t layernorm_ws_bytes(int B, int HW, int C) {
-    const RowSplit rs = plan_rows(B, HW);
-    return ((size_t)B * rs.chunks * 2 + (size_t)B * rs.chunks * 2 * C + (size_t)2 * B + 16) * sizeof(float);
-}
-
 template <typename T>
 int layernorm_fwd_t(const T* x, const float* gamma, const float* beta, T* y, float* mean, float* inv, int B, int HW,
                       int C, float eps, int act, void* ws, size_t ws_bytes, void* stream, unsigned long long* amax = nullptr,
                       unsigned amax_ep = 0) {
     if (!norm_shape_ok(B, HW, C, VecOf<T>::V) || (size_t)HW * C < 2 || !norm_act_ok(act)) return DWC_EINVAL;
-    if (!ws || ws_bytes < layernorm_ws_bytes(B, HW, C)) return DWC_EWORKSPACE;
+    const LayerNormScratch sc(B, HW, C);
+    if (!ws || ws_bytes < sc.bytes) return DWC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const RowSplit rs = plan_rows(B, HW);
     float* part = (float*)ws;
-    hipLaunchKernelGGL(ln_stats_partial<T>, dim3(rs.chunks, B), dim3(256), 0, st, x, part, HW, C, rs.rows_per_chunk);
+    hipLaunchKernelGGL(ln_stats_partial<T>, dim3(sc.rs.chunks, B), dim3(256), 0, st, x, part, HW, C, sc.rs.rows_per_chunk);
     DWC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ln_stats_final<T>, dim3((B + 63) / 64), dim3(64), 0, st, x, part, mean, inv, B, HW, C, rs.chunks, eps);
+    hipLaunchKernelGGL(ln_stats_final<T>, dim3((B + 63) / 64), dim3(64), 0, st, x, part, mean, inv, B, HW, C, sc.rs.chunks, eps);
     DWC_LAUNCH_CHECK();
     const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
     NORM_LAUNCH_ACT(act, ln_apply, (T), dim3(ra.chunks, B), dim3(256), 0, st, x, mean, inv, gamma, beta, y, HW, C, ra.rows_per_chunk,
@@ -1169,17 +1164,17 @@ int layernorm_bwd_t(const T* dy, const T* x, const float* mean, const float* inv
                     const float* beta, T* dx, float* dgamma, float* dbeta, int B, int HW, int C, float eps, int act,
                       void* ws, size_t ws_bytes, void* stream, unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
     if (!norm_shape_ok(B, HW, C, VecOf<T>::V) || !norm_act_ok(act)) return DWC_EINVAL;
-    if (!ws || ws_bytes < layernorm_ws_bytes(B, HW, C)) return DWC_EWORKSPACE;
+    const LayerNormScratch sc(B, HW, C);
+    if (!ws || ws_bytes < sc.bytes) return DWC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const RowSplit rs = plan_rows(B, HW);
     float* part_s = (float*)ws;
-    float* part_c = part_s + (size_t)B * rs.chunks * 2;
-    float* sums = part_c + (size_t)B * rs.chunks * 2 * C;
-    NORM_LAUNCH_ACT(act, ln_bwd_partial, (T), dim3(rs.chunks, B), dim3(256), 0, st, dy, x, mean, inv, gamma, beta, part_s, part_c, HW,
-                    C, rs.rows_per_chunk, act);
+    float* part_c = part_s + sc.part_c;
+    float* sums = part_s + sc.sums;
+    NORM_LAUNCH_ACT(act, ln_bwd_partial, (T), dim3(sc.rs.chunks, B), dim3(256), 0, st, dy, x, mean, inv, gamma, beta, part_s, part_c, HW,
+                    C, sc.rs.rows_per_chunk, act);
     DWC_LAUNCH_CHECK();
     hipLaunchKernelGGL(ln_bwd_final, dim3(B + (C + 63) / 64), dim3(1024), 0, st, part_s, part_c, sums, dgamma, dbeta, B, C,
-                       rs.chunks);
+                       sc.rs.chunks);
     DWC_LAUNCH_CHECK();
     const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
     NORM_LAUNCH_ACT(act, ln_bwd_apply, (T), dim3(ra.chunks, B), dim3(256), 0, st, dy, x, mean, inv, gamma, beta, sums, dx, HW, C,
@@ -1187,10 +1182,6 @@ int layernorm_bwd_t(const T* dy, const T* x, const float* mean, const float* inv
     DWC_LAUNCH_CHECK();
     return DWC_OK;
 }
-
-}  // namespace
-
-namespace {
 
 // ---------------------------------------------------------------------------------------
 // batch norm over S equal batch segments (nn.BatchNorm2d of Conv2dBlock(norm='bn'), reference networks.py:547)
@@ -1236,21 +1227,7 @@ __global__ __launch_bounds__(1024) void bn_stats_final(const T* __restrict__ x, 
                 const size_t n = (size_t)s * Bs + i;
                 const float* p = part + n * chunks * C + c;
                 float a = 0.f, b = 0.f;
-                int k = 0;
-                for (; k + 4 <= chunks; k += 4) {              // (four pairs in flight, summed in chunk order)
-                    float va[4], vb[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        va[u] = p[(size_t)(k + u) * C];
-                        vb[u] = p[plane + (size_t)(k + u) * C];
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) a += va[u], b += vb[u];
-                }
-                for (; k < chunks; ++k) {
-                    a += p[(size_t)k * C];
-                    b += p[plane + (size_t)k * C];
-                }
+                strided_sum2<4>(p, plane, C, 0, 1, chunks, a, b);      // (four pairs in flight, summed in chunk order)
                 const float dn = ((float)x[n * HW * C + c] - p0) + a / hw;
                 bn_merge(cnt, d, m2, hw, dn, fmaxf(b - a * (a / hw), 0.f));
             }
@@ -1297,10 +1274,8 @@ __global__ __launch_bounds__(256) void bn_apply(const T* __restrict__ x, const f
                                                 int Bs, int HW, int C, int rows_per_chunk, int act, unsigned long long* amax = nullptr,
                                                 unsigned amax_ep = 0) {
     constexpr int V = VecOf<T>::V;
-    const int cq = C / V;
-    const int groups = 256 / cq;
-    const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
-    // (threads past the last row group walk no rows below but still reach the publish barrier)
+    const RowGeom<V> geo(C);
+    const int cq = geo.cq, groups = geo.groups, col = geo.col, rg = geo.rg;
     unsigned am = 0;
     const int n = blockIdx.y;
     const size_t s = (size_t)(n / Bs) * C + col * V;
@@ -1369,9 +1344,8 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(const T* __restrict__ dy, 
                                                       int rows_per_chunk, size_t plane, int act) {
     constexpr int V = VecOf<T>::V;
     __shared__ float sm[2 * 256 * V];
-    const int cq = C / V;
-    const int groups = 256 / cq;
-    const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
+    const RowGeom<V> geo(C);
+    const int cq = geo.cq, groups = geo.groups, col = geo.col, rg = geo.rg;
     const int n = blockIdx.y, chunk = blockIdx.x;
     const size_t base = (size_t)n * HW * cq + col;
     const size_t s = (size_t)(n / Bs) * C + col * V;
@@ -1421,7 +1395,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(const T* __restrict__ dy, 
             acc(x0, d0);
         }
     }
-    colsum_groups<V>(s1, s2, sm, groups, cq, col, rg);
+    colsum_groups<V>(s1, s2, sm, geo);
     if (rg == 0) {
         const size_t o = ((size_t)n * gridDim.x + chunk) * C + col * V;
         stf<V>(part, o, s1);
@@ -1441,24 +1415,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_final(const float* __restrict__ p
     float dg = 0.f, db = 0.f;
     for (int s = 0; s < S; ++s) {
         float a = 0.f, b = 0.f;
-        if (c < C) {
-            const float* p = part + (size_t)s * total * C + c;
-            int k = g;
-            for (; k + 3 * 16 < total; k += 4 * 16) {
-                float va[4], vb[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    va[u] = p[(size_t)(k + 16 * u) * C];
-                    vb[u] = p[plane + (size_t)(k + 16 * u) * C];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) a += va[u], b += vb[u];
-            }
-            for (; k < total; k += 16) {
-                a += p[(size_t)k * C];
-                b += p[plane + (size_t)k * C];
-            }
-        }
+        if (c < C) strided_sum2<4>(part + (size_t)s * total * C + c, plane, C, g, 16, total, a, b);
         __syncthreads();                                       // lane 0 has read the previous segment's partials
         sm[0][g][cl] = a;
         sm[1][g][cl] = b;
@@ -1489,10 +1446,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const T* __restrict__ dy, co
                                                     int S, int Bs, int HW, int C, int rows_per_chunk, int act, int coupled,
                                                     unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
     constexpr int V = VecOf<T>::V;
-    const int cq = C / V;
-    const int groups = 256 / cq;
-    const int col = threadIdx.x % cq, rg = threadIdx.x / cq;
-    // (threads past the last row group walk no rows below but still reach the publish barrier)
+    const RowGeom<V> geo(C);
+    const int cq = geo.cq, groups = geo.groups, col = geo.col, rg = geo.rg;
     unsigned am = 0;
     const int n = blockIdx.y;
     const size_t s = (size_t)(n / Bs) * C + col * V;
@@ -1560,12 +1515,6 @@ bool bn_shape_ok(int S, int Bs, int HW, int C, int V) {
     return S >= 1 && S <= DWC_BN_MAX_SEGMENTS && Bs > 0 && HW > 0 && C >= V && C % V == 0 && C / V <= 256 && (long)S * Bs <= 65535;
 }
 
-size_t batchnorm_ws_bytes(int S, int Bs, int HW, int C) {      // two planes of partials + two planes of per-(segment, channel) sums
-    if (S < 1 || Bs < 1 || HW < 1 || C < 1) return 0;
-    const RowSplit rs = plan_rows(Bs, HW);
-    return ((size_t)2 * S * Bs * rs.chunks * C + (size_t)2 * S * C + 16) * sizeof(float);
-}
-
 template <typename T>
 int batchnorm_fwd_t(const T* x, const float* gamma, const float* beta, float* running_mean, float* running_var, T* y, float* mean,
                     float* rstd, int S, int Bs, int HW, int C, float eps, float momentum, int act, int training, dwc_bn_order order,
@@ -1578,14 +1527,13 @@ int batchnorm_fwd_t(const T* x, const float* gamma, const float* beta, float* ru
     const int B = S * Bs;
     if (training) {
         if ((long)Bs * HW < 2) return DWC_EINVAL;
-        if (!ws || ws_bytes < batchnorm_ws_bytes(S, Bs, HW, C)) return DWC_EWORKSPACE;
-        const RowSplit rs = plan_rows(Bs, HW);
-        const size_t plane = (size_t)B * rs.chunks * C;
+        const BatchNormScratch sc(S, Bs, HW, C);
+        if (!ws || ws_bytes < sc.bytes) return DWC_EWORKSPACE;
         float* part = (float*)ws;
-        hipLaunchKernelGGL(in_stats_partial<T>, dim3(rs.chunks, B), dim3(256), 0, st, x, part, HW, C, rs.rows_per_chunk, plane);
+        hipLaunchKernelGGL(in_stats_partial<T>, dim3(sc.rs.chunks, B), dim3(256), 0, st, x, part, HW, C, sc.rs.rows_per_chunk, sc.plane);
         DWC_LAUNCH_CHECK();
         hipLaunchKernelGGL(bn_stats_final<T>, dim3((C + 63) / 64), dim3(1024), 0, st, x, part, mean, rstd, running_mean, running_var, S,
-                           Bs, HW, C, rs.chunks, plane, eps, momentum, order);
+                           Bs, HW, C, sc.rs.chunks, sc.plane, eps, momentum, order);
         DWC_LAUNCH_CHECK();
     } else {
         if (S != 1 || !running_mean) return DWC_EINVAL;
@@ -1605,17 +1553,16 @@ int batchnorm_bwd_t(const T* dy, const T* x, const float* mean, const float* rst
                     void* stream, unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
     if (!bn_shape_ok(S, Bs, HW, C, VecOf<T>::V) || !dwc_act_is_simple_host(act) || act < 0) return DWC_EINVAL;
     if (training ? (long)Bs * HW < 2 : S != 1) return DWC_EINVAL;
-    if (!ws || ws_bytes < batchnorm_ws_bytes(S, Bs, HW, C)) return DWC_EWORKSPACE;
+    const BatchNormScratch sc(S, Bs, HW, C);
+    if (!ws || ws_bytes < sc.bytes) return DWC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int B = S * Bs;
-    const RowSplit rs = plan_rows(Bs, HW);
-    const size_t plane = (size_t)B * rs.chunks * C;
     float* part = (float*)ws;
-    float* sums = part + 2 * plane;
-    hipLaunchKernelGGL(bn_bwd_partial<T>, dim3(rs.chunks, B), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, part, Bs, HW, C,
-                       rs.rows_per_chunk, plane, act);
+    float* sums = part + sc.sums;
+    hipLaunchKernelGGL(bn_bwd_partial<T>, dim3(sc.rs.chunks, B), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, part, Bs, HW, C,
+                       sc.rs.rows_per_chunk, sc.plane, act);
     DWC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_bwd_final, dim3((C + 63) / 64), dim3(1024), 0, st, part, sums, dgamma, dbeta, S, Bs, C, rs.chunks, plane);
+    hipLaunchKernelGGL(bn_bwd_final, dim3((C + 63) / 64), dim3(1024), 0, st, part, sums, dgamma, dbeta, S, Bs, C, sc.rs.chunks, sc.plane);
     DWC_LAUNCH_CHECK();
     const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
     hipLaunchKernelGGL(bn_bwd_apply<T>, dim3(ra.chunks, B), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, sums, dx, S, Bs, HW, C,
@@ -1628,7 +1575,9 @@ int batchnorm_bwd_t(const T* dy, const T* x, const float* mean, const float* rst
 
 extern "C" {
 
-size_t dwc_batchnorm_ws_bytes(int S, int Bs, int HW, int C) { return batchnorm_ws_bytes(S, Bs, HW, C); }
+size_t dwc_batchnorm_ws_bytes(int S, int Bs, int HW, int C) {
+    return S < 1 || Bs < 1 || HW < 1 || C < 1 ? 0 : BatchNormScratch(S, Bs, HW, C).bytes;
+}
 
 int dwc_batchnorm_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, float* y,
                       float* mean, float* rstd, int S, int Bs, int HW, int C, float eps, float momentum, int act, int training,
@@ -1670,8 +1619,8 @@ int dwc_bf16_batchnorm_bwd(const void* dy, const void* x, const float* mean, con
 /* 1 when `act` is an activation code the instance-norm / layer-norm / linear_small entry points fuse (host only, no launch) */
 int dwc_norm_act_ok(int act) { return norm_act_ok(act) ? 1 : 0; }
 
-size_t dwc_instnorm_ws_bytes(int B, int HW, int C) { return instnorm_ws_bytes(B, HW, C); }
-size_t dwc_layernorm_ws_bytes(int B, int HW, int C) { return layernorm_ws_bytes(B, HW, C); }
+size_t dwc_instnorm_ws_bytes(int B, int HW, int C) { return InstNormScratch(B, HW, C).bytes; }
+size_t dwc_layernorm_ws_bytes(int B, int HW, int C) { return LayerNormScratch(B, HW, C).bytes; }
 
 int dwc_instnorm_fwd(const float* x, const float* gamma, const float* beta, const float* residual, float* y, float* mean,
                      float* rstd, int B, int HW, int C, float eps, int act, void* ws, size_t ws_bytes, void* stream) {

@@ -66,14 +66,11 @@ class _BatchNorm(torch.autograd.Function):
         rstd = torch.empty(S * C, dtype=torch.float32, device=dev)
         ws = ops.workspace(lib.dwc_batchnorm_ws_bytes(S, Bs, H * W, C), dev)
         desc = _lib.BnOrder(len(order), (ctypes.c_int * MAX_SEGMENTS)(*order))
-        head = (x.data_ptr(), ops._p(gamma), ops._p(beta), ops._p(running_mean), ops._p(running_var), y.data_ptr(), mean.data_ptr(),
-                rstd.data_ptr(), S, Bs, H * W, C, eps, momentum, act, int(training), desc, ws.data_ptr(), ws.numel())
-        ya, yep = ops.out_amax(y)
-        if ya is not None:
-            _lib.check(lib.dwc_batchnorm_fwd_amax(*head, ya, yep, ops._stream()), "batchnorm_fwd")
-            ops.set_amax(y, ya, yep)
-        else:
-            _lib.check(ops._fn(lib, "batchnorm_fwd", x)(*head, ops._stream()), "batchnorm_fwd")
+        amax = ops._norm_call("batchnorm_fwd", x, y, (x.data_ptr(), ops._p(gamma), ops._p(beta), ops._p(running_mean), ops._p(running_var),
+                                                      y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), S, Bs, H * W, C, eps, momentum, act,
+                                                      int(training), desc, ws.data_ptr(), ws.numel()))
+        if amax:
+            ops.set_amax(y, *amax)
         ops._hbm("batchnorm_fwd", x.numel() * x.element_size() * (3 if training else 2))
         if training and running_mean is not None and len(order):
             torch.autograd.graph.increment_version([running_mean, running_var])      # (written through raw pointers)
@@ -94,14 +91,11 @@ class _BatchNorm(torch.autograd.Function):
         dgamma = torch.empty(C, dtype=torch.float32, device=dev) if gamma is not None and ctx.needs_input_grad[1] else None
         dbeta = torch.empty(C, dtype=torch.float32, device=dev) if beta is not None and ctx.needs_input_grad[2] else None
         ws = ops.workspace(lib.dwc_batchnorm_ws_bytes(S, Bs, H * W, C), dev)
-        head = (dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ops._p(gamma), ops._p(beta), dx.data_ptr(), ops._p(dgamma),
-                ops._p(dbeta), S, Bs, H * W, C, act, training, ws.data_ptr(), ws.numel())
-        da, dep = ops.out_amax(dx)
-        if da is not None:
-            _lib.check(lib.dwc_batchnorm_bwd_amax(*head, da, dep, ops._stream()), "batchnorm_bwd")
-            ops.set_amax(dx, da, dep)
-        else:
-            _lib.check(ops._fn(lib, "batchnorm_bwd", x)(*head, ops._stream()), "batchnorm_bwd")
+        amax = ops._norm_call("batchnorm_bwd", x, dx, (dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ops._p(gamma), ops._p(beta),
+                                                       dx.data_ptr(), ops._p(dgamma), ops._p(dbeta), S, Bs, H * W, C, act, training,
+                                                       ws.data_ptr(), ws.numel()))
+        if amax:
+            ops.set_amax(dx, *amax)
         ops._hbm("batchnorm_bwd", x.numel() * x.element_size() * 5)
         return dx, dgamma, dbeta, None, None, None, None, None, None, None, None
 

@@ -1816,6 +1816,20 @@ def lstm_bidir(x, lens, w_ih, w_hh, b_ih, b_hh, owners=None):
 # --------------------------------------------------------------------------------------
 # norms
 # --------------------------------------------------------------------------------------
+def _norm_call(name, x, out, args):
+    """``dwc_<name>`` of csrc/norm.hip in x's precision on ``args`` (the C argument list without the absmax pair and the stream).  When
+    ``out``, the tensor the call writes, is given an absmax slot, the ``_amax`` entry point raises it from the apply pass and the
+    (slot, epoch) pair comes back for the caller to tag ``out`` with (the tagging stays at the call site: tests/test_amax_contract.py
+    tells the producers apart by it); else None."""
+    lib = _lib.load()
+    slot, ep = out_amax(out)
+    if slot is None:
+        _lib.check(_fn(lib, name, x)(*args, _stream()), name)
+        return None
+    _lib.check(getattr(lib, "dwc_%s_amax" % name)(*args, slot, ep, _stream()), name)
+    return slot, ep
+
+
 class _InstNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, act, eps, token=None):
@@ -1833,16 +1847,10 @@ class _InstNorm(torch.autograd.Function):
         mean = torch.empty(B * C, dtype=torch.float32, device=dev)
         rstd = torch.empty(B * C, dtype=torch.float32, device=dev)
         ws = workspace(lib.dwc_instnorm_ws_bytes(B, H * W, C), dev)
-        ya, yep = out_amax(y)
-        if ya is not None:
-            _lib.check(lib.dwc_instnorm_fwd_amax(x.data_ptr(), _p(gamma), _p(beta), _p(residual), y.data_ptr(), mean.data_ptr(),
-                                                 rstd.data_ptr(), B, H * W, C, eps, int(act), ws.data_ptr(), ws.numel(),
-                                                 ya, yep, _stream()), "instnorm_fwd")
-            set_amax(y, ya, yep)
-        else:
-            _lib.check(_fn(lib, "instnorm_fwd", x)(x.data_ptr(), _p(gamma), _p(beta), _p(residual), y.data_ptr(), mean.data_ptr(),
-                                                   rstd.data_ptr(), B, H * W, C, eps, int(act), ws.data_ptr(), ws.numel(),
-                                                   _stream()), "instnorm_fwd")
+        amax = _norm_call("instnorm_fwd", x, y, (x.data_ptr(), _p(gamma), _p(beta), _p(residual), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                                 B, H * W, C, eps, int(act), ws.data_ptr(), ws.numel()))
+        if amax:
+            set_amax(y, *amax)
         _hbm("instnorm_fwd", x.numel() * x.element_size() * (3 if residual is not None else 2))
         ctx.save_for_backward(x, mean, rstd, gamma, beta)
         ctx.act = int(act)
@@ -1862,16 +1870,10 @@ class _InstNorm(torch.autograd.Function):
             dgamma = torch.empty(B * C, dtype=torch.float32, device=dev)
             dbeta = torch.empty(B * C, dtype=torch.float32, device=dev)
         ws = workspace(lib.dwc_instnorm_ws_bytes(B, H * W, C), dev)
-        da, dep = out_amax(dx)
-        if da is not None:
-            _lib.check(lib.dwc_instnorm_bwd_amax(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _p(gamma), _p(beta),
-                                                 dx.data_ptr(), _p(dgamma), _p(dbeta), B, H * W, C, ctx.act, ws.data_ptr(),
-                                                 ws.numel(), da, dep, _stream()), "instnorm_bwd")
-            set_amax(dx, da, dep)
-        else:
-            _lib.check(_fn(lib, "instnorm_bwd", x)(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _p(gamma), _p(beta),
-                                                   dx.data_ptr(), _p(dgamma), _p(dbeta), B, H * W, C, ctx.act, ws.data_ptr(),
-                                                   ws.numel(), _stream()), "instnorm_bwd")
+        amax = _norm_call("instnorm_bwd", x, dx, (dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _p(gamma), _p(beta), dx.data_ptr(),
+                                                  _p(dgamma), _p(dbeta), B, H * W, C, ctx.act, ws.data_ptr(), ws.numel()))
+        if amax:
+            set_amax(dx, *amax)
         _hbm("instnorm_bwd", x.numel() * x.element_size() * 3)
         if ctx.token is not None:                 # the first convolution of the block adds it in its data-gradient epilogue
             ctx.token.g = dy
@@ -1899,16 +1901,10 @@ class _LayerNorm(torch.autograd.Function):
         mean = torch.empty(B, dtype=torch.float32, device=dev)
         inv = torch.empty(B, dtype=torch.float32, device=dev)
         ws = workspace(lib.dwc_layernorm_ws_bytes(B, H * W, C), dev)
-        ya, yep = out_amax(y)
-        if ya is not None:
-            _lib.check(lib.dwc_layernorm_fwd_amax(x.data_ptr(), g.data_ptr(), b.data_ptr(), y.data_ptr(), mean.data_ptr(), inv.data_ptr(),
-                                                  B, H * W, C, eps, int(act), ws.data_ptr(), ws.numel(), ya, yep, _stream()),
-                       "layernorm_fwd")
-            set_amax(y, ya, yep)
-        else:
-            _lib.check(_fn(lib, "layernorm_fwd", x)(x.data_ptr(), g.data_ptr(), b.data_ptr(), y.data_ptr(), mean.data_ptr(),
-                                                    inv.data_ptr(), B, H * W, C, eps, int(act), ws.data_ptr(), ws.numel(), _stream()),
-                       "layernorm_fwd")
+        amax = _norm_call("layernorm_fwd", x, y, (x.data_ptr(), g.data_ptr(), b.data_ptr(), y.data_ptr(), mean.data_ptr(), inv.data_ptr(), B, H * W,
+                                                  C, eps, int(act), ws.data_ptr(), ws.numel()))
+        if amax:
+            set_amax(y, *amax)
         _hbm("layernorm_fwd", x.numel() * x.element_size() * 2)
         ctx.save_for_backward(x, mean, inv, g, b)
         ctx.act, ctx.eps = int(act), eps
@@ -1925,16 +1921,11 @@ class _LayerNorm(torch.autograd.Function):
         dgamma = torch.empty(C, dtype=torch.float32, device=dev)
         dbeta = torch.empty(C, dtype=torch.float32, device=dev)
         ws = workspace(lib.dwc_layernorm_ws_bytes(B, H * W, C), dev)
-        da, dep = out_amax(dx)
-        if da is not None:
-            _lib.check(lib.dwc_layernorm_bwd_amax(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), inv.data_ptr(), g.data_ptr(),
-                                                  b.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), B, H * W, C,
-                                                  ctx.eps, ctx.act, ws.data_ptr(), ws.numel(), da, dep, _stream()), "layernorm_bwd")
-            set_amax(dx, da, dep)
-        else:
-            _lib.check(_fn(lib, "layernorm_bwd", x)(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), inv.data_ptr(), g.data_ptr(),
-                                                    b.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), B, H * W, C,
-                                                    ctx.eps, ctx.act, ws.data_ptr(), ws.numel(), _stream()), "layernorm_bwd")
+        amax = _norm_call("layernorm_bwd", x, dx, (dy.data_ptr(), x.data_ptr(), mean.data_ptr(), inv.data_ptr(), g.data_ptr(), b.data_ptr(),
+                                                   dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), B, H * W, C, ctx.eps, ctx.act,
+                                                   ws.data_ptr(), ws.numel()))
+        if amax:
+            set_amax(dx, *amax)
         _hbm("layernorm_bwd", x.numel() * x.element_size() * 3)
         return dx, dgamma, dbeta, None, None
 

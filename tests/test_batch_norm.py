@@ -43,6 +43,8 @@ SHAPES = [
     (3, 2, 128, 9),       # HW 81, ragged chunk
     (2, 1, 1024, 3),      # one row group
     (2, 5, 256, 32),
+    (1, 2, 512, 5),       # HW 25: the unrolled walk and its tail in one workgroup; apply chunks of 8 / 16 rows, the last one tail only
+    (1, 2, 24, 6),        # idle row groups: bf16 3 column groups x 85 row groups, thread 255 idles; fp32 6 x 42, four idle threads
 ]
 
 
@@ -552,7 +554,7 @@ def _assert_tag(t, slot, ep, what):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("where", ["first", "last"])
-@pytest.mark.parametrize("shape", [(1, 2, 8, 6), (3, 2, 128, 9), (4, 2, 64, 16)], ids=ids_x)
+@pytest.mark.parametrize("shape", [(1, 2, 8, 6), (3, 2, 128, 9), (4, 2, 64, 16), (1, 2, 12, 6)], ids=ids_x)      # (C = 12: 3 x 85 threads walk rows, thread 255 idles up to the publish barrier)
 def test_bn_absmax_slots(slots, shape, where):
     """The tag of y and of dx equals max|t| bit for bit, with a peak planted in the first / the last pixel of the last sample (the
     ends of a row walk: the first row of the first row group, the last row of a ragged last chunk)."""

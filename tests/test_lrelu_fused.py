@@ -60,7 +60,9 @@ def ids_x(s):
 # ---- 1. instance norm / AdaIN + lrelu (+ residual) against the oracle expression ------------------------------------------------------
 # (B, C, H): resident HW 256 / resident HW 1024 with an odd number of workgroup pairs / multi-pass, one column group / 4-pixel planes
 # (D's tail) / multi-pass
-IN_SHAPES = [(2, 64, 16), (3, 64, 32), (2, 8, 6), (2, 512, 2), (1, 128, 8)]
+# (2, 512, 5): HW 25 is no resident plane; the statistics and backward-partial walks run their unrolled loop and a tail in one workgroup,
+# the apply walks split it into chunks of 8 (bf16: 16) rows -- unrolled loop only -- and a last chunk that is tail only
+IN_SHAPES = [(2, 64, 16), (3, 64, 32), (2, 8, 6), (2, 512, 2), (1, 128, 8), (2, 512, 5)]
 IN_SHAPES_BF16 = IN_SHAPES + [(2, 128, 16), (1, 128, 32)]            # the bf16 resident branch at C = 128 as well (C = 64 above)
 IN_MODES = ["in_lrelu", "adain_lrelu", "adain_lrelu_res"]
 
@@ -140,7 +142,7 @@ def test_instance_norm_relu_argument_still_means_relu():
 # ---- 2. MUNIT layer norm + lrelu -----------------------------------------------------------------------------------------------------
 @gpu
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
-@pytest.mark.parametrize("shape", [(3, 128, 16), (1, 64, 32), (2, 8, 10)], ids=ids_x)
+@pytest.mark.parametrize("shape", [(3, 128, 16), (1, 64, 32), (2, 8, 10), (2, 512, 5)], ids=ids_x)      # (2, 512, 5): see IN_SHAPES
 def test_layer_norm_lrelu(prec, shape):
     B, C, H = shape
     half = prec == "bf16"
