@@ -716,19 +716,19 @@ struct Im2colBF16 {
         int splits, chunk;
         if (!ws || ws_bytes < wgrad_ws_bytes(g.M, g.K, Cout, WGRAD_SLAB_ROWS, &splits, &chunk)) return DWC_EWORKSPACE;
         float* slab = (float*)ws;
-        const int tk = (g.K + 127) / 128;
+        const int tk = (g.K + 127) / 128, bn = wgrad_bn(Cout);
 #ifdef DWC_DEV_ABLATIONS      // timing-only ablations (WRONG results): compiled only by `make ABLATIONS=1`, never in the shipped .so
         static const int dbg = getenv("DWC_WGRAD_DBG") ? atoi(getenv("DWC_WGRAD_DBG")) : 0;
-        if (Cout > 64 && dbg) {
+        if (bn == 128 && dbg) {
 #define WG_DBG(D) case D: hipLaunchKernelGGL((wgrad_kernel_h<128, 2, 2, 2, 2, D>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk); break;
             switch (dbg) { WG_DBG(1) WG_DBG(2) WG_DBG(3) WG_DBG(4) WG_DBG(7) default: return DWC_EINVAL; }
 #undef WG_DBG
         } else
 #endif
-        if (Cout > 64) {
+        if (bn == 128) {
             hipLaunchKernelGGL((wgrad_kernel_h<128, 2, 2, 2, 2>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy, Cout, slab,
                                chunk);
-        } else if (Cout > 32) {
+        } else if (bn == 64) {
             hipLaunchKernelGGL((wgrad_kernel_h<64, 2, 2, 2, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
         } else {
             hipLaunchKernelGGL((wgrad_kernel_h<32, 4, 1, 1, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);

@@ -109,11 +109,15 @@ __global__ __launch_bounds__(256) void wgrad_reduce_wide_kernel(const float* __r
     dw[((size_t)co * cin_real + ci) * KHW + tap] = s;
 }
 
-// (host) true when the wide form was launched: few elements, many splits
+// (host) the shapes the wide form takes: few elements, many splits.  The one statement of the rule: wgrad_reduce_wide launches by it and
+// the plan queries of conv_im2col_entry.h report it.
+inline bool wgrad_reduce_takes_wide(int splits, int K, int N) { return splits >= 16 && (size_t)K * N <= 262144; }
+
+// (host) true when the wide form was launched
 inline bool wgrad_reduce_wide(const float* slab, float* dw, int splits, int K, int N, int Cin, int KHW, int cin_real, int cout_real,
                               hipStream_t st) {
     const size_t total = (size_t)K * N;
-    if (splits < 16 || total > 262144) return false;
+    if (!wgrad_reduce_takes_wide(splits, K, N)) return false;
     hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, slab, dw, splits, K, N, Cin, KHW,
                        cin_real, cout_real);
     return true;
@@ -205,13 +209,16 @@ bool conv_args_ok(int B, int H, int W, int Cin, int Cout, int KH, int KW, int st
     return true;
 }
 
+// Column tile of the weight-gradient kernels: which of the three instantiations wgrad_launch picks (fp32 and bf16 alike).
+inline int wgrad_bn(int N) { return N > 64 ? 128 : (N > 32 ? 64 : 32); }
+
 // Split of the pixel contraction of the weight gradient into `splits` ranges of `chunk` rows (a multiple of the
 // 32-row slab).  Every workgroup of a launch does the same amount of work, so the launch takes
 // rounds * (slabs per workgroup + prologue/epilogue) where a round is one full set of resident workgroups: the
 // split count is chosen to fill 1..4 rounds EXACTLY rather than to reach a fixed number of workgroups (29 ranges x
 // 36 tiles = 1044 workgroups is two rounds plus a third for the last 20).
 void wgrad_plan(int M, int K, int N, int* splits, int* chunk, int classes = 1, int slab_rows = 32) {
-    const int bn = N > 64 ? 128 : (N > 32 ? 64 : 32);
+    const int bn = wgrad_bn(N);
     const long resident = bn == 128 ? 2 : (bn == 64 ? 3 : 4);       // workgroups per CU by LDS footprint
     const long tiles = (long)((K + 127) / 128) * ((N + bn - 1) / bn) * classes;
     const long slots = NUM_CU * resident;

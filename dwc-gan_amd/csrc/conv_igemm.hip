@@ -691,19 +691,19 @@ struct Im2colF32 {
         int splits, chunk;
         if (!ws || ws_bytes < wgrad_ws_bytes(g.M, g.K, Cout, WGRAD_SLAB_ROWS, &splits, &chunk)) return DWC_EWORKSPACE;
         float* slab = (float*)ws;
-        const int tk = (g.K + 127) / 128;
+        const int tk = (g.K + 127) / 128, bn = wgrad_bn(Cout);
         if (wgrad_x3_on()) {
-            if (Cout > 64)
+            if (bn == 128)
                 hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2, true>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
                                    Cout, slab, chunk);
-            else if (Cout > 32)
+            else if (bn == 64)
                 hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
             else
                 hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-        } else if (Cout > 64) {
+        } else if (bn == 128) {
             hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
                                Cout, slab, chunk);
-        } else if (Cout > 32) {
+        } else if (bn == 64) {
             hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
         } else {
             hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);

@@ -61,6 +61,20 @@ size_t im2col_fwd_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int K
     return gemm_ws_bytes(im2col_plan<P>(f.g.M, Cout, f.g.K, 1), f.dst_elems);
 }
 
+// The Plan im2col_fwd hands to launch_gemm for this shape, out = {bm, bn, splits, kt_per_split}: the same checks, the same fwd_geom and
+// the same im2col_plan call, nothing launched.  (launch_gemm runs that plan as it stands, except that a split plan without its scratch
+// runs unsplit and that the fp32 split-product form runs a 128x128 plan on the 128x64 kernel.)  For tests: they assert the branch they
+// claim to cover instead of carrying a copy of the planner.
+template <class P>
+int im2col_fwd_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int* out) {
+    FwdGeom f;
+    if (!out || (Cout & P::CH_MASK) || !fwd_geom(nullptr, nullptr, B, H, W, Cin, Cout, KH, KW, stride, pad, &f, P::MIN_LOG_C))
+        return DWC_EINVAL;
+    const Plan p = im2col_plan<P>(f.g.M, f.o.N, f.g.K, 1);
+    out[0] = p.bm; out[1] = p.bn; out[2] = p.splits; out[3] = p.kt_per_split;
+    return DWC_OK;
+}
+
 // reflect != 0: reflect pad + convolution (+ bias, + activation).  reflect == 0, the zero-padded convolutions (the frozen VGG16 of
 // the perceptual loss, reference networks.py:639-688: nn.Conv2d(padding=1)): the same kernel with the zero rule.
 template <class P>
@@ -245,6 +259,20 @@ int im2col_bwd_weight(const void* x, const void* dy, float* dw_oihw, int B, int 
                            (hipStream_t)stream);
 }
 
+// What im2col_bwd_weight launches for this shape, out = {bn, splits, chunk, wide_reduce}: the column tile of the kernel wgrad_launch
+// picks (wgrad_bn: 128 / 64 / 32), the pixel split of wgrad_ws_bytes and whether wgrad_reduce takes the wide form
+// (wgrad_reduce_takes_wide).  Nothing launched; DWC_EINVAL where im2col_bwd_weight returns it for the shape alone.
+template <class P>
+int im2col_bwd_weight_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int* out) {
+    FwdGeom f;
+    if (!out || (Cout & P::CH_MASK) || !fwd_geom(nullptr, nullptr, B, H, W, Cin, Cout, KH, KW, stride, pad, &f, P::MIN_LOG_C))
+        return DWC_EINVAL;
+    int splits, chunk;
+    wgrad_ws_bytes(f.g.M, f.g.K, Cout, P::WGRAD_SLAB_ROWS, &splits, &chunk);
+    out[0] = wgrad_bn(Cout); out[1] = splits; out[2] = chunk; out[3] = wgrad_reduce_takes_wide(splits, f.g.K, Cout) ? 1 : 0;
+    return DWC_OK;
+}
+
 // with per-axis stride and reflect pad
 template <class P>
 size_t im2col_bwd_weight_ex_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride_h, int stride_w, int pad_h,
@@ -284,6 +312,12 @@ int im2col_bwd_weight_ex(const void* x, const void* dy, float* dw_oihw, int B, i
     }                                                                                                                                    \
     size_t NAME(conv2d_fwd_ws_bytes)(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {                      \
         return im2col_fwd_ws_bytes<P>(B, H, W, Cin, Cout, KH, KW, stride, pad);                                                          \
+    }                                                                                                                                    \
+    int NAME(conv2d_fwd_plan)(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int* out) {                   \
+        return im2col_fwd_plan<P>(B, H, W, Cin, Cout, KH, KW, stride, pad, out);                                                         \
+    }                                                                                                                                    \
+    int NAME(conv2d_bwd_weight_plan)(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int* out) {            \
+        return im2col_bwd_weight_plan<P>(B, H, W, Cin, Cout, KH, KW, stride, pad, out);                                                  \
     }                                                                                                                                    \
     int NAME(conv2d_fwd)(const X* x, const X* w, const float* bias, X* y, int B, int H, int W, int Cin, int Cout, int KH, int KW,        \
                          int stride, int pad, int act, void* ws, size_t ws_bytes, void* stream) {                                        \

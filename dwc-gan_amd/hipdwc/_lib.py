@@ -221,9 +221,14 @@ SIGNATURES = {
     "dwc_batchnorm_bwd_amax": (c_int, [c_fp] * 9 + [c_int] * 6 + [c_fp, c_sz, c_fp, c_u, c_fp]),
     "dwc_bf16_batchnorm_fwd": (c_int, [c_fp] * 8 + [c_int] * 4 + [c_f, c_f, c_int, c_int, BnOrder, c_fp, c_sz, c_fp]),
     "dwc_bf16_batchnorm_bwd": (c_int, [c_fp] * 9 + [c_int] * 6 + [c_fp, c_sz, c_fp]),
+    # ---- plan queries of the im2col entry layer (ABI 11; host code only): out = int[4], see plan() ----
+    "dwc_conv2d_fwd_plan": (c_int, [c_int] * 9 + [c_fp]),
+    "dwc_conv2d_bwd_weight_plan": (c_int, [c_int] * 9 + [c_fp]),
+    "dwc_bf16_conv2d_fwd_plan": (c_int, [c_int] * 9 + [c_fp]),
+    "dwc_bf16_conv2d_bwd_weight_plan": (c_int, [c_int] * 9 + [c_fp]),
 }
 
-ABI_VERSION = 10               # DWC_ABI_VERSION of include/dwcgan_hip.h
+ABI_VERSION = 11             # DWC_ABI_VERSION of include/dwcgan_hip.h
 EINVAL = -1
 _ERRORS = {-1: "DWC_EINVAL (unsupported shape/argument)", -2: "DWC_EWORKSPACE (scratch too small)",
            -3: "DWC_ELAUNCH (kernel launch failed)"}
@@ -269,3 +274,11 @@ def load():
 def check(rc, what):
     if rc != 0:
         raise HipKernelError("%s failed: %s" % (what, _ERRORS.get(rc, rc)))
+
+
+def plan(name, *shape):
+    """The four ints a plan query (`dwc_conv2d_fwd_plan`, `dwc_bf16_conv2d_bwd_weight_plan`, ...) reports for `shape` = (B, H, W, Cin,
+    Cout, KH, KW, stride, pad).  Host code only: no device is needed.  Raises where the entry point refuses the shape."""
+    out = (c_int * 4)()
+    check(getattr(load(), name)(*shape, out), name)
+    return tuple(out)

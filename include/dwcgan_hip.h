@@ -48,7 +48,7 @@ extern "C" {
 /* Version of this C ABI: bumped with every change of an entry point's signature or of a structure passed through it (r05: 5 --
  * dwc_weight_refresh_multi gained has_h2 / epoch, the dwc_h2_* / dwc_*_amax entry points).  A binding must refuse a library that
  * reports another number: symbols alone do not tell a changed argument list (hipdwc/_lib.py does). */
-#define DWC_ABI_VERSION 10
+#define DWC_ABI_VERSION 11
 int dwc_version(void);
 /* The fp32 im2col kernels (dwc_conv2d_fwd / _bwd_data* / _bwd_weight*, ring strips) take their inner products as exact three-way
  * bf16 split products on the bf16 matrix cores by default (r04; fp32 operands, results and accumulation -- see
@@ -139,6 +139,18 @@ int dwc_conv2d_bwd_weight_ex(const float* x, const float* dy, float* dw_oihw,
                              int B, int H, int W, int Cin, int Cout, int KH, int KW,
                              int stride_h, int stride_w, int pad_h, int pad_w,
                              int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream);
+/* (ABI 11) Plan queries: host code only, nothing is launched and no pointer but `out` is touched.  They report which kernel
+ * instantiation and which split the entry point of the same shape runs, so that a test can assert the branch it covers.
+ * dwc_conv2d_fwd_plan: out = {bm, bn, splits, kt_per_split}, the output tile, the number of K ranges (1: unsplit) and the K-slabs
+ * (32 deep) per range that dwc_conv2d_fwd / _zeropad plan for this shape.  The launch follows the plan except that a split plan
+ * without its scratch runs unsplit, and that the split-product form (dwc_x3_gemm_mode bit 0, K >= 128) runs a 128 x 128 plan on
+ * its 128 x 64 kernel.
+ * dwc_conv2d_bwd_weight_plan: out = {bn, splits, chunk, wide_reduce}, the column tile of the weight-gradient kernel (128: Cout > 64,
+ * 64: Cout 33..64, 32: Cout <= 32), the number of pixel ranges and the pixels per range (scratch: splits slabs of [K][Cout] floats),
+ * and 1 when the slabs are summed by the wide reduce (>= 16 ranges of at most 262144 elements), 0 for the plain one.
+ * Both return DWC_EINVAL for the shapes the entry point refuses, DWC_OK otherwise. */
+int dwc_conv2d_fwd_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int out[4]);
+int dwc_conv2d_bwd_weight_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int out[4]);
 /* g = dy * act'(y) and db[c] = sum over rows of g (rows = B*Ho*Wo).  db may be NULL. */
 size_t dwc_act_bwd_bias_ws_bytes(int rows, int C);
 int dwc_act_bwd_bias(const float* dy, const float* y, float* g, float* db, int rows, int C, int act,
@@ -515,6 +527,10 @@ int dwc_bf16_conv2d_fwd(const void* x, const void* w_prepared, const float* bias
                         int Cout, int KH, int KW, int stride, int pad, int act, void* ws, size_t ws_bytes, void* stream);
 int dwc_bf16_conv2d_fwd_ex(const void* x, const void* w_prepared, const float* bias, void* y, int B, int H, int W, int Cin,
                            int Cout, int KH, int KW, int stride_h, int stride_w, int pad_h, int pad_w, int act, void* stream);
+/* (ABI 11) the plan queries of dwc_conv2d_fwd_plan / dwc_conv2d_bwd_weight_plan for the bf16 kernels: tiles up to 256 x 256, 64-deep
+ * K-slabs, 64-pixel weight-gradient slabs */
+int dwc_bf16_conv2d_fwd_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int out[4]);
+int dwc_bf16_conv2d_bwd_weight_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int out[4]);
 size_t dwc_bf16_conv2d_bwd_data_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
 int dwc_bf16_conv2d_bwd_data(const void* dy, const void* w_dgrad, void* dxp, int B, int H, int W, int Cin, int Cout, int KH,
                              int KW, int stride, int pad, void* ws, size_t ws_bytes, void* stream);

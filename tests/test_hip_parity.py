@@ -184,87 +184,6 @@ def test_alternative_paths_agree(prec, switch):
         ops.set_precision("fp32")
 
 
-# (entry point[:branch], k, stride, pad, Cin, Cout in fp32, Cout in bf16) at B = 1, H = W = 8; Cin 0: an image (4 / 8 planes).
-# Cout is the smallest count that takes the branch: the split-K fold needs 8 K-slabs (9 * 32 / 32, 9 * 64 / 64), same_dgrad_geom
-# needs Cout >= 32 and >= one K-slab (32 / 64), image_dgrad_geom Cout >= 32.
-IM2COL_DGRAD_CASES = [
-    ("bwd_data_fold:direct", 3, 1, 1, 8, 8, 8),
-    ("bwd_data_fold:splitk", 3, 1, 1, 8, 32, 64),
-    ("bwd_data_same", 3, 1, 1, 8, 32, 64),
-    ("bwd_data_same", 5, 1, 2, 8, 32, 64),
-    ("bwd_data_ring", 3, 1, 1, 8, 32, 64),
-    ("bwd_data_ring", 5, 1, 2, 8, 32, 64),
-    ("bwd_data_s2_ring", 4, 2, 1, 8, 8, 8),
-    ("bwd_data_image", 7, 1, 3, 0, 32, 32),
-]
-
-
-@pytest.mark.parametrize("prec", ["fp32", "bf16"])
-@pytest.mark.parametrize("case", IM2COL_DGRAD_CASES, ids=lambda c: "%s-k%d" % (c[0].replace(":", "-"), c[1]))
-def test_im2col_data_gradient_entry_points(case, prec):
-    """Every data-gradient entry point of the im2col files (csrc/conv_im2col_entry.h), called through the C ABI itself so that no
-    path selection of ops.py stands between the test and the export, in both precisions and on both branches of bwd_data_fold
-    (direct: interior cropped into dx + band fold; split-K: padded image + whole-image fold).  Against the float64 gradient of the
-    reflect-padded convolution.  The ring entry points add the folded border ring to a dx that already holds the interior: the test
-    supplies the float64 interior (the crop of the padded image's gradient)."""
-    what, k, s, p, ci, co32, co16 = case
-    half = prec == "bf16"
-    B, H = 1, 8
-    ops.set_precision(prec)
-    try:
-        lib = _lib_mod.load()
-        dt = ops.act_dtype()
-        co, ci = (co16 if half else co32), ci or ops.image_planes(dt)
-        rnd = (lambda t: t.to(torch.bfloat16).float()) if half else (lambda t: t)
-        g = torch.Generator().manual_seed(k + 10 * p + co)
-        w = torch.randn(co, ci, k, k, generator=g) * (1.0 / (co * k * k) ** 0.5)
-        Ho = (H + 2 * p - k) // s + 1
-        gy = rnd(torch.randn(B, co, Ho, Ho, generator=g))
-        xr = torch.zeros(B, ci, H, H, dtype=torch.float64, requires_grad=True)       # (the gradient does not depend on x)
-        xp = torch.nn.functional.pad(xr, (p, p, p, p), mode="reflect")
-        xp.retain_grad()
-        (torch.nn.functional.conv2d(xp, rnd(w).double(), None, stride=s) * gy.double()).sum().backward()
-        ref, inner = xr.grad.float(), xp.grad[:, :, p:-p, p:-p].float()
-        assert (ref - inner).abs().max().item() > 0.1 * ref.abs().max().item()       # the ring matters at this size
-
-        gd = gy.to(DEV).to(dt).contiguous(memory_format=torch.channels_last)
-        wd = w.to(DEV)
-        dx = ops.empty_cl(B, ci, H, H, gd.device, dt)
-        st, Hp = ops._stream(), H + 2 * p
-        fn = lambda name: ops._fn(lib, "conv2d_" + name, gd)
-        prepped = lambda kind: ops._prepped(wd, kind, co, ci, s, None, half).data_ptr()
-        scratch = lambda n: torch.empty(max(int(n), 1), dtype=torch.uint8, device=DEV)
-        name = what.split(":")[0]
-        if name == "bwd_data_fold":
-            nws = fn("bwd_data_ws_bytes")(B, H, H, ci, co, k, k, s, p)
-            assert (nws > 0) == what.endswith("splitk"), (what, nws)
-            dxp, ws = scratch(B * Hp * Hp * ci * dx.element_size()), scratch(nws)
-            rc = fn(name)(gd.data_ptr(), prepped("dgrad"), dxp.data_ptr(), dx.data_ptr(), B, H, H, ci, co, k, k, s, p,
-                          ws.data_ptr() if nws else None, nws, st)
-        elif name in ("bwd_data_same", "bwd_data_ring"):
-            nws = fn("bwd_data_same_ws_bytes")(B, H, H, ci, co, k, k, p)
-            assert nws > 0
-            ws = scratch(nws)
-            if name == "bwd_data_ring":
-                dx.copy_(inner)
-            rc = fn(name)(gd.data_ptr(), prepped("dgrad"), prepped("dgrad_t"), dx.data_ptr(), B, H, H, ci, co, k, k, p, ws.data_ptr(),
-                          nws, st)
-        elif name == "bwd_data_s2_ring":
-            dxp = scratch(B * Hp * Hp * ci * dx.element_size())
-            dx.copy_(inner)
-            rc = fn(name)(gd.data_ptr(), prepped("dgrad"), dxp.data_ptr(), dx.data_ptr(), B, H, H, ci, co, st)
-        else:
-            nws = fn("bwd_data_image_ws_bytes")(B, H, H, co, k, k, p)
-            assert nws > 0
-            ws = scratch(nws)
-            rc = fn(name)(gd.data_ptr(), prepped("dgrad_image"), dx.data_ptr(), B, H, H, co, k, k, p, ws.data_ptr(), nws, st)
-        _lib_mod.check(rc, name)
-        # (the dx tolerances of test_conv_forward_backward and of tests/test_bf16_parity.py: a stored bf16 tensor)
-        close(dx, ref, rel=6e-3 if half else 5e-5, msg=what)
-    finally:
-        ops.set_precision("fp32")
-
-
 # (Cin, Cout, H, k, stride, pad): generic GEMM (stride 2), split-product 3x3 and 5x5; bf16: halo 3x3, generic
 NONFINITE_SHAPES = [(64, 64, 16, 4, 2, 1), (256, 256, 16, 3, 1, 1), (128, 64, 16, 5, 1, 2)]
 

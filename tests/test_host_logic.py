@@ -132,6 +132,38 @@ def test_library_exports_every_declared_symbol():
     assert _lib.load().dwc_conv2d_bwd_weight_ws_bytes(2, 8, 8, 16, 16, 3, 3, 1, 1) >= 9 * 16 * 16 * 4
 
 
+def test_plan_queries_agree_with_the_scratch_sizes():
+    """dwc_[bf16_]conv2d_fwd_plan / _bwd_weight_plan are host code: they answer without a device, refuse what the entry points refuse,
+    and their splits are the ones the *_ws_bytes functions size the scratch for."""
+    lib = _lib.load()
+    shapes = [(3, 4, 4, 256, 128, 4, 4, 1, 0), (7, 32, 32, 256, 512, 1, 1, 1, 0), (4, 96, 96, 16, 192, 3, 3, 1, 1), (2, 21, 19, 16, 40, 3, 3, 1, 1),
+              (8, 32, 32, 16, 64, 3, 3, 1, 1), (2, 64, 64, 128, 256, 4, 4, 2, 1)]
+    for pre, bk, slab in (("dwc_", 32, 32), ("dwc_bf16_", 64, 64)):
+        for s in shapes:
+            B, H, W, ci, co, kh, kw, st, p = s
+            M = B * ((H + 2 * p - kh) // st + 1) * ((W + 2 * p - kw) // st + 1)
+            K = kh * kw * ci
+            bm, bn, splits, kt = _lib.plan(pre + "conv2d_fwd_plan", *s)
+            assert bm > 0 and bn > 0 and splits >= 1 and (splits - 1) * kt < (K + bk - 1) // bk <= splits * kt
+            assert getattr(lib, pre + "conv2d_fwd_ws_bytes")(*s) == (splits * M * co * 4 if splits > 1 else 0)
+            wbn, wsplits, chunk, wide = _lib.plan(pre + "conv2d_bwd_weight_plan", *s)
+            assert wbn >= min(co, 128) and chunk % slab == 0              # (one column tile up to 128 channels)
+            assert (wsplits - 1) * chunk < M <= wsplits * chunk and wide in (0, 1)
+            assert not (wide and wsplits == 1)                             # (a single range has nothing to reduce widely)
+            assert getattr(lib, pre + "conv2d_bwd_weight_ws_bytes")(*s) == wsplits * K * co * 4
+        out = (ctypes.c_int * 4)(*([-7] * 4))
+        for bad in ((0, 8, 8, 16, 16, 3, 3, 1, 1), (1, 8, 8, 12, 16, 3, 3, 1, 1), (1, 8, 8, 16, 16, 3, 3, 3, 1), (1, 8, 8, 16, 16, 3, 3, 1, 8),
+                    (1, 8, 8, 16, 18, 3, 3, 1, 1)):
+            assert getattr(lib, pre + "conv2d_fwd_plan")(*bad, out) == _lib.EINVAL
+            assert getattr(lib, pre + "conv2d_bwd_weight_plan")(*bad, out) == _lib.EINVAL
+        assert list(out) == [-7] * 4
+        assert getattr(lib, pre + "conv2d_fwd_plan")(1, 8, 8, 16, 16, 3, 3, 1, 1, None) == _lib.EINVAL
+    # 4 output channels: a multiple of 4 is enough for fp32, bf16 needs 8
+    assert lib.dwc_conv2d_fwd_plan(1, 8, 8, 16, 4, 3, 3, 1, 1, out) == 0
+    assert lib.dwc_bf16_conv2d_fwd_plan(1, 8, 8, 16, 4, 3, 3, 1, 1, out) == _lib.EINVAL
+    assert lib.dwc_bf16_conv2d_bwd_weight_plan(1, 8, 8, 16, 4, 3, 3, 1, 1, out) == _lib.EINVAL
+
+
 def test_no_cpu_fallback():
     x = torch.randn(1, 4, 8, 8)
     w = torch.randn(8, 4, 3, 3)
