@@ -409,7 +409,9 @@ __device__ __forceinline__ int tr_swizzle(int m) {
     return CPRW == 16 ? 4 * (m & 3) : (CPRW == 8 ? 4 * ((m >> 1) & 1) : 0);
 }
 
-template <int BN, int WM, int WN, int TM, int TN, int DBG = 0>     // DBG: timing ablations (1 no MFMA, 2 no operand reads, 4 no staging)
+// ZP: the zero rule (weight gradient of a zero-padded convolution): a gathered pixel outside the image takes an offset past the
+// descriptor and reads as zeros (OOB of gemm_body_h).  A compile-time rule: the reflect instantiations are the instructions they were.
+template <int BN, int WM, int WN, int TM, int TN, int DBG = 0, bool ZP = false>     // DBG: timing ablations (1 no MFMA, 2 no operand reads, 4 no staging)
 __global__ __launch_bounds__(256) void wgrad_kernel_h(Gather g, const bf16* __restrict__ dy, int N, float* __restrict__ slab,
                                                       int m_chunk) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -473,9 +475,16 @@ __global__ __launch_bounds__(256) void wgrad_kernel_h(Gather g, const bf16* __re
                 oh = rem / g.OW;
                 ow = rem - oh * g.OW;
             }
-            const int h = reflect_idx(oh * g.mul_h + dh, g.SH);
-            const int w = reflect_idx(ow * g.mul_w + dw, g.SW);
-            const unsigned off = ((unsigned)(((n * g.SH + h) * g.SW + w) << g.logSC) + (unsigned)ci) * 2u;
+            unsigned off;
+            if constexpr (ZP) {
+                const int h = oh * g.mul_h + dh, w = ow * g.mul_w + dw;
+                const bool inb = (unsigned)h < (unsigned)g.SH && (unsigned)w < (unsigned)g.SW;
+                off = inb ? ((unsigned)(((n * g.SH + h) * g.SW + w) << g.logSC) + (unsigned)ci) * 2u : 0x80000000u;
+            } else {
+                const int h = reflect_idx(oh * g.mul_h + dh, g.SH);
+                const int w = reflect_idx(ow * g.mul_w + dw, g.SW);
+                off = ((unsigned)(((n * g.SH + h) * g.SW + w) << g.logSC) + (unsigned)ci) * 2u;
+            }
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(la + i * 16 * 128), 16, off, 0,
                                                      0, 0);
         }
@@ -657,6 +666,7 @@ struct Im2colBF16 {
     static constexpr int BK = ::BK;
     static constexpr int MIN_LOG_C = ::MIN_LOG_C;
     static constexpr int CH_MASK = 7;
+    static constexpr bool ZERO_BY_OFFSET = true;    // out-of-image rows take the offset OOB = 2^31
     static constexpr bool HALF_STRIPS = true;       // the 128-row strip tile exists (strip_bm)
     static constexpr int WGRAD_SLAB_ROWS = 64;
     static constexpr int IMAGE_PX = 4;              // NHWC8 images: 4 pixels x 8 planes (2 groups of 4) per GEMM row
@@ -725,7 +735,15 @@ struct Im2colBF16 {
 #undef WG_DBG
         } else
 #endif
-        if (bn == 128) {
+        if (!g.reflect) {          // the zero-rule instantiations (conv2d_bwd_weight_zeropad)
+            if (bn == 128)
+                hipLaunchKernelGGL((wgrad_kernel_h<128, 2, 2, 2, 2, 0, true>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
+                                   Cout, slab, chunk);
+            else if (bn == 64)
+                hipLaunchKernelGGL((wgrad_kernel_h<64, 2, 2, 2, 1, 0, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+            else
+                hipLaunchKernelGGL((wgrad_kernel_h<32, 4, 1, 1, 1, 0, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+        } else if (bn == 128) {
             hipLaunchKernelGGL((wgrad_kernel_h<128, 2, 2, 2, 2>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy, Cout, slab,
                                chunk);
         } else if (bn == 64) {

@@ -49,6 +49,30 @@ int fold_reflect(const T* gp, T* dx, int B, int H, int W, int C4, int pad, int W
     return DWC_OK;
 }
 
+// zero-pad adjoint: the interior of the padded gradient image gp ([B][H+2pad][W+2pad][C]) copied to dx ([B][H][W][C]), groups of 4
+// channels.  For the data gradients of zero-padded convolutions whose GEMM could not write the interior itself (split-K).
+template <typename T>
+__global__ void crop_image_kernel(const T* __restrict__ gp, T* __restrict__ dx, int B, int H, int W, int C4, int pad) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t total = (size_t)B * H * W * C4;
+    if (idx >= total) return;
+    const int c = idx % C4;
+    size_t r = idx / C4;
+    const int w = r % W;
+    r /= W;
+    const int h = r % H;
+    const size_t n = r / H;
+    st4(dx, idx, ld4(gp, ((n * (H + 2 * pad) + h + pad) * (size_t)(W + 2 * pad) + w + pad) * C4 + c));
+}
+
+template <typename T>
+int crop_image(const T* gp, T* dx, int B, int H, int W, int C4, int pad, hipStream_t st) {
+    const size_t total = (size_t)B * H * W * C4;
+    hipLaunchKernelGGL(crop_image_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, gp, dx, B, H, W, C4, pad);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+
 // dx (holds the interior of the padded gradient image already: Scatter::crop) += the border ring of gp folded back by the reflect
 // rule; only the pixels a ring pixel folds onto are visited (rows 1..pad and H-1-pad..H-2 whole, columns 1..pad and W-1-pad..W-2
 // of the other rows).  CV = C / VecOf<T>::V channel groups of 16 bytes.

@@ -82,7 +82,9 @@ struct WgradHaloArgs {
 // with no MFMA running, by the probes of conv_narrow_persist_kernel); with one half issuing, the other half's MFMAs run meanwhile.  Worth
 // 3-4 % on the 5x5 form (LDS read bandwidth still bounds it), nothing on the stride-2 one, and the 3x3 form has no register left for
 // it (256 in use: 11 spilled, 166 -> 179 us): instantiated for KS == 5 only.
-template <int KS, int BN, int DBG = 0, int PROBE = 0, int PFT = -1, int SPREAD = 0, int HALF = 0>
+// ZP: the zero rule (weight gradient of a zero-padded convolution): a patch pixel outside the image takes the out-of-range offset
+// that reads as zeros, like the pixels past the patch.  A compile-time rule: the reflect instantiations are the instructions they were.
+template <int KS, int BN, int DBG = 0, int PROBE = 0, int PFT = -1, int SPREAD = 0, int HALF = 0, bool ZP = false>
 __global__ __launch_bounds__(512) void wgrad_halo_kernel(WgradHaloArgs a, unsigned long long* probe = nullptr) {
 #if defined(__HIP_DEVICE_COMPILE__)
     unsigned long long stamp[4] = {0, 0, 0, 0};
@@ -160,11 +162,15 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(WgradHaloArgs a, unsign
         for (int i = 0; i < PPASS; ++i) {
             const int pp = t / PCH + P_RPP * i;
             const int py = pp / PW, px = pp - py * PW;
-            const int h = min(reflect_idx(S2 ? 2 * (y0 + py) + par_y - 1 : y0 - PAD + py, a.H), a.H - 1);
-            const int w = min(reflect_idx(S2 ? 2 * (x0 + px) + par_x - 1 : x0 - PAD + kw0 + px, a.W), a.W - 1);
+            const int hr = S2 ? 2 * (y0 + py) + par_y - 1 : y0 - PAD + py;
+            const int wr = S2 ? 2 * (x0 + px) + par_x - 1 : x0 - PAD + kw0 + px;
+            const int h = min(reflect_idx(hr, a.H), a.H - 1);
+            const int w = min(reflect_idx(wr, a.W), a.W - 1);
             const int lc = (t % PCH) ^ p_swz(pp);
             const unsigned off = ((unsigned)(((n * a.H + h) * a.W + w) << a.logCin) + (unsigned)(cs * CIW + lc * 8)) * 2u;
-            s_off[i] = pp < PPIX ? off : OOB;
+            bool ok = pp < PPIX;
+            if constexpr (ZP) ok = ok && (unsigned)hr < (unsigned)a.H && (unsigned)wr < (unsigned)a.W;
+            s_off[i] = ok ? off : OOB;
         }
 #pragma unroll
         for (int p = 0; p < D_PASSES; ++p) {
@@ -525,13 +531,13 @@ int dwc_bf16_conv2d_s2_halo_ok(int B, int H, int W, int Cin, int Cout) {
 /* y = act(conv4x4_stride2(reflect_pad1(x)) + bias) on bf16 NHWC tensors (reference networks.py:90,94,437, networks_v2.py:107-111):
  * x [B,H,W,Cin] -> y [B,H/2,W/2,Cout]; w prepared by dwc_bf16_weight_prepare_fwd (KH = KW = 4, cout_pad = Cout, cin_pad = Cin).
  * Halo form over the space-to-depth image (conv_halo16_bf16.inc, S2), two 4-wave workgroups per CU.  No scratch. */
-int dwc_bf16_conv2d_s2_halo(const void* x, const void* w_prepared, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
-                            int act, void* stream) {
+static int s2_halo_run(const void* x, const void* w_prepared, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
+                       int act, void* stream, int reflect) {
     if (!x || !w_prepared || !y || !dwc_bf16_conv2d_s2_halo_ok(B, H, W, Cin, Cout)) return DWC_EINVAL;
     HaloArgs a;
     a.x = (const bf16*)x; a.w = (const bf16*)w_prepared; a.bias = bias; a.add = nullptr; a.y = (bf16*)y;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.logCin = dwc_ilog2_exact(Cin); a.N = Cout; a.K = 4;
-    a.Kp = (16 * Cin + BK - 1) / BK * BK; a.act = act; a.reflect = 1;
+    a.Kp = (16 * Cin + BK - 1) / BK * BK; a.act = act; a.reflect = reflect;
     a.blocks_x = (W / 2) / TB; a.blocks_per_img = ((H / 2) / TB) * ((W / 2) / TB);
     hipStream_t st = (hipStream_t)stream;
     const int nblk = B * a.blocks_per_img;
@@ -546,6 +552,18 @@ int dwc_bf16_conv2d_s2_halo(const void* x, const void* w_prepared, const float* 
     return DWC_OK;
 }
 
+int dwc_bf16_conv2d_s2_halo(const void* x, const void* w_prepared, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
+                            int act, void* stream) {
+    return s2_halo_run(x, w_prepared, bias, y, B, H, W, Cin, Cout, act, stream, 1);
+}
+
+/* the same forward of the ZERO-padded layer: the kernel's patch map takes the rule per input-pixel parity (HaloArgs::reflect = 0: a
+ * pixel of row -1 / row H, or of those columns, takes the out-of-range offset).  Shapes of dwc_bf16_conv2d_s2_halo_ok. */
+int dwc_bf16_conv2d_s2_halo_zeropad(const void* x, const void* w_prepared, const float* bias, void* y, int B, int H, int W, int Cin,
+                                    int Cout, int act, void* stream) {
+    return s2_halo_run(x, w_prepared, bias, y, B, H, W, Cin, Cout, act, stream, 0);
+}
+
 size_t dwc_bf16_conv2d_wgrad_halo_ws_bytes(int B, int H, int W, int Cin, int Cout, int K) {
     const int bn = wgrad_halo_bn(B, H, W, Cin, Cout, K);
     if (!bn) return 0;
@@ -557,8 +575,8 @@ size_t dwc_bf16_conv2d_wgrad_halo_ws_bytes(int B, int H, int W, int Cin, int Cou
 /* dw (fp32 OIHW, [cout_real][cin_real][K][K]) of a reflect-padded stride-1 "same" K x K convolution (K = 3, 5) from x:[B,H,W,Cin]
  * and dy:[B,H,W,Cout], or of the 4x4 stride-2 reflect-pad-1 convolution (K = 4; dy:[B,H/2,W/2,Cout]) -- both bf16, halo form (see
  * wgrad_halo_kernel); dwc_bf16_conv2d_wgrad_halo_ws_bytes == 0 means the shape is not handled (use dwc_bf16_conv2d_bwd_weight). */
-int dwc_bf16_conv2d_wgrad_halo(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int K,
-                               int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream) {
+static int wgrad_halo_run(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int K, int cin_real,
+                          int cout_real, void* ws, size_t ws_bytes, void* stream, bool zero) {
     const int bn = wgrad_halo_bn(B, H, W, Cin, Cout, K);
     if (!bn || cin_real > Cin || cout_real > Cout) return DWC_EINVAL;
     int splits, ups;
@@ -581,7 +599,14 @@ int dwc_bf16_conv2d_wgrad_halo(const void* x, const void* dy, float* dw_oihw, in
     // stride-2 form 160 -> 166 us and stays as it was, profiles/r06_wgrad_half_ab.txt.  DWC_WGRAD_HALF=0 restores the all-waves burst.)
     const char* he = getenv("DWC_WGRAD_HALF");
     const int half = he ? atoi(he) : 1;
-    if (K == 3) hipLaunchKernelGGL((wgrad_halo_kernel<3, 128>), grid, dim3(512), 0, st, a);
+    if (zero) {        // the zero-rule instantiations (dwc_bf16_conv2d_wgrad_halo_zeropad)
+        if (K == 3) hipLaunchKernelGGL((wgrad_halo_kernel<3, 128, 0, 0, -1, 0, 0, true>), grid, dim3(512), 0, st, a);
+        else if (K == 4) hipLaunchKernelGGL((wgrad_halo_kernel<4, 128, 0, 0, -1, 0, 0, true>), grid, dim3(512), 0, st, a);
+        else if (bn == 128 && half) hipLaunchKernelGGL((wgrad_halo_kernel<5, 128, 0, 0, -1, 0, 1, true>), grid, dim3(512), 0, st, a);
+        else if (bn == 128) hipLaunchKernelGGL((wgrad_halo_kernel<5, 128, 0, 0, -1, 0, 0, true>), grid, dim3(512), 0, st, a);
+        else if (half) hipLaunchKernelGGL((wgrad_halo_kernel<5, 64, 0, 0, -1, 0, 1, true>), grid, dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((wgrad_halo_kernel<5, 64, 0, 0, -1, 0, 0, true>), grid, dim3(512), 0, st, a);
+    } else if (K == 3) hipLaunchKernelGGL((wgrad_halo_kernel<3, 128>), grid, dim3(512), 0, st, a);
     else if (K == 4) hipLaunchKernelGGL((wgrad_halo_kernel<4, 128>), grid, dim3(512), 0, st, a);
     else if (bn == 128 && half) hipLaunchKernelGGL((wgrad_halo_kernel<5, 128, 0, 0, -1, 0, 1>), grid, dim3(512), 0, st, a);
     else if (bn == 128) hipLaunchKernelGGL((wgrad_halo_kernel<5, 128>), grid, dim3(512), 0, st, a);
@@ -594,6 +619,19 @@ int dwc_bf16_conv2d_wgrad_halo(const void* x, const void* dy, float* dw_oihw, in
                        K * K * Cin, Cout, Cin, K * K, cin_real, cout_real);
     DWC_LAUNCH_CHECK();
     return DWC_OK;
+}
+
+int dwc_bf16_conv2d_wgrad_halo(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int K,
+                               int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream) {
+    return wgrad_halo_run(x, dy, dw_oihw, B, H, W, Cin, Cout, K, cin_real, cout_real, ws, ws_bytes, stream, false);
+}
+
+/* the same weight gradient of the ZERO-padded convolution (pad (K-1)/2 at stride 1, pad 1 for the 4x4 stride-2 layer): shapes, plan
+ * and scratch of dwc_bf16_conv2d_wgrad_halo */
+int dwc_bf16_conv2d_wgrad_halo_zeropad(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int K,
+                                       int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !dy || !dw_oihw) return DWC_EINVAL;
+    return wgrad_halo_run(x, dy, dw_oihw, B, H, W, Cin, Cout, K, cin_real, cout_real, ws, ws_bytes, stream, true);
 }
 
 }  // extern "C"

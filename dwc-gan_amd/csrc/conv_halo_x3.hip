@@ -155,8 +155,14 @@ struct X3Args {
 // stores them as n extra patch rows and columns; the fragment address of lane (row, column) under tap (kh, kw) gets a per-lane offset
 // (two registers per pixel tile for the rows, two for the columns, selected by the tap).  No extra MFMA.  See conv_halo16_bf16.inc
 // for the bf16 twin.
-template <int KS, int BN, int WM, int WN, int TM, int TN, int DBG = 0, int PB = 2, int S2 = 0, int KSP = 1, int NPL = 3, int RING = 0>
+// ZP (S2 == 1 only): the zero rule of the stride-2 forward.  Input row -1 (row parity 0 of the first patch row) and row H (row parity 1
+// of the last one), and the columns alike, are invalid: a per-pass validity mask per parity travels next to the row / column deltas
+// and sends the load to the offset that reads as zero (RAW) or zeroes the value at the LDS write.  A compile-time rule: the reflect
+// instantiations are the instructions they were.
+template <int KS, int BN, int WM, int WN, int TM, int TN, int DBG = 0, int PB = 2, int S2 = 0, int KSP = 1, int NPL = 3, int RING = 0,
+          bool ZP = false>
 __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 1) void conv_halo_x3_kernel(X3Args a) {
+    static_assert(!ZP || S2 == 1, "ZP is the stride-2 forward's zero rule (the other forms take X3Args::reflect)");
 #if defined(__HIP_DEVICE_COMPILE__)
     // 8 waves, two per SIMD, one workgroup per CU -- or 4 waves and two workgroups per CU (PB == 1).  (4 "fat" waves, one per
     // SIMD with up to 512 registers -- 4x2 tiles, a second fragment set, all latency hiding inside the wave's own instruction
@@ -270,6 +276,8 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 1) void conv_halo_
     int p_base[S2 == 1 ? PPASS : 1], p_drow[S2 == 1 ? PPASS : 1], p_dcol[S2 == 1 ? PPASS : 1];
     int p_dst[PPASS];                                   // LDS element offset of (py, px), channels 4*(t&3)..
     unsigned p_ok = 0, p_in = 0;                        // loads are unconditional (the vmcnt arithmetic below counts them)
+    unsigned z_r0 = 0, z_r1 = 0, z_c0 = 0, z_c1 = 0;    // ZP: bit i = pass i gathers outside the image for row / column parity 0 / 1
+    unsigned pv_bad = 0;                                // ZP: the passes of the slab held in pv that read as zero
 #pragma unroll
     for (int i = 0; i < PPASS; ++i) {
         const int pp = (t >> 2) + PPT * i;
@@ -281,6 +289,12 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 1) void conv_halo_
             p_base[i] = ((n_img * a.H + h0) * a.W + w0) * a.Cin;
             p_drow[i] = (h1 - h0) * a.W * a.Cin;
             p_dcol[i] = (w1 - w0) * a.Cin;
+            if constexpr (ZP) {
+                z_r0 |= 2 * (y0 + py) - 1 < 0 ? 1u << i : 0u;
+                z_r1 |= 2 * (y0 + py) >= a.H ? 1u << i : 0u;
+                z_c0 |= 2 * (x0 + px) - 1 < 0 ? 1u << i : 0u;
+                z_c1 |= 2 * (x0 + px) >= a.W ? 1u << i : 0u;
+            }
         } else {
             int h = y0 - PAD + py, w = x0 - PAD + px;
             if constexpr (S2 == 2) {
@@ -311,10 +325,14 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 1) void conv_halo_
                 const int par = cs / ncsr, csl = cs - par * ncsr;
                 const int my = -(par >> 1), mx = -(par & 1);
                 const int soff = __builtin_amdgcn_readfirstlane(csl * CS * 4);
+                unsigned bad = 0;
+                if constexpr (ZP) bad = (my ? z_r1 : z_r0) | (mx ? z_c1 : z_c0);
 #pragma unroll
-                for (int i = 0; i < PPASS; ++i)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(lr + i * THREADS * 8), 16,
-                                                             (unsigned)(p_base[i] + (p_drow[i] & my) + (p_dcol[i] & mx) + (t & 3) * 4) * 4u, soff, 0, 0);
+                for (int i = 0; i < PPASS; ++i) {
+                    unsigned off = (unsigned)(p_base[i] + (p_drow[i] & my) + (p_dcol[i] & mx) + (t & 3) * 4) * 4u;
+                    if constexpr (ZP) off = (bad >> i) & 1 ? 0x80000000u : off;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(lr + i * THREADS * 8), 16, off, soff, 0, 0);
+                }
             } else {
                 const int soff = __builtin_amdgcn_readfirstlane(cs * CS * 4);
 #pragma unroll
@@ -326,6 +344,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 1) void conv_halo_
             const int par = cs / ncsr, csl = cs - par * ncsr;
             const float* base = a.x + csl * CS + (t & 3) * 4;
             const int my = -(par >> 1), mx = -(par & 1);
+            if constexpr (ZP) pv_bad = (my ? z_r1 : z_r0) | (mx ? z_c1 : z_c0);      // (the clamped addresses are loaded all the same)
 #pragma unroll
             for (int i = 0; i < PPASS; ++i) pv[i] = *reinterpret_cast<const f32x4*>(base + (p_base[i] + (p_drow[i] & my) + (p_dcol[i] & mx)));
         } else {
@@ -340,7 +359,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 1) void conv_halo_
             if (!((p_in >> i) & 1)) continue;                             // slot past the patch
             f32x4 v;
             if constexpr (RAW) v = *reinterpret_cast<const f32x4*>(sR + (i * THREADS + t) * 8);      // (this lane's own DMA: zeros where the rule says so)
-            else v = (p_ok >> i) & 1 ? pv[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+            else v = ((p_ok & ~pv_bad) >> i) & 1 ? pv[i] : f32x4{0.f, 0.f, 0.f, 0.f};
             const Planes<NPL> q = split_planes<NPL>(v, sx.s);
 #pragma unroll
             for (int pl = 0; pl < NPL; ++pl) *reinterpret_cast<u32x2*>(dst + pl * P_PLANE + p_dst[i]) = q.p[pl];
@@ -968,7 +987,10 @@ struct X3WgradArgs {
 
 // CIW = 64: 8 waves, one workgroup per CU.  CIW = 32: 4 waves, <= 74 KB of LDS, TWO independent workgroups per CU (see
 // conv_halo_x3_kernel: they drift out of phase and overlap each other's MFMA and load phases).
-template <int KS, int BN, int CIW = 64, int AHEAD = 2, int NPL = 3>
+// ZP: the zero rule (weight gradient of a zero-padded convolution): a patch pixel outside the image is gathered at the offset that
+// reads as zero (2^31, as conv_halo_x3_kernel's RAW gather).  A compile-time rule: the reflect instantiations are the instructions
+// they were.
+template <int KS, int BN, int CIW = 64, int AHEAD = 2, int NPL = 3, bool ZP = false>
 // (two planes, K = 3 / 4: two 8-wave workgroups per CU -- four waves per SIMD, at most 128 registers -- see x3_wgrad_plan)
 __global__ __launch_bounds__(CIW == 64 ? 512 : 256, CIW == 64 ? (NPL == 2 && KS != 5 ? 4 : 1) : 2) void wgrad_x3_kernel(X3WgradArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1055,12 +1077,15 @@ __global__ __launch_bounds__(CIW == 64 ? 512 : 256, CIW == 64 ? (NPL == 2 && KS 
     f32x4 pv[2];
     auto load_patch = [&](UnitPos q, int first) {      // passes first, first+1 of the unit at q into pv[]
         const int y0 = q.uy * UH, x0 = q.ux * UW;
-        const int w = min(reflect_idx(S2 ? 2 * (x0 + pcol) + kw - 1 : x0 - PAD + kw + pcol, a.W), a.W - 1);
+        const int wr = S2 ? 2 * (x0 + pcol) + kw - 1 : x0 - PAD + kw + pcol;
+        const int w = min(reflect_idx(wr, a.W), a.W - 1);
         const unsigned img = (unsigned)q.n * img_bytes;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int h = min(reflect_idx((S2 ? 2 * y0 - 1 : y0 - PAD) + prow + 2 * (first + j), a.H), a.H - 1);
-            const unsigned off = (unsigned)((h * a.W + w) * a.Cin) * 4u + x_lane;
+            const int hr = (S2 ? 2 * y0 - 1 : y0 - PAD) + prow + 2 * (first + j);
+            const int h = min(reflect_idx(hr, a.H), a.H - 1);
+            unsigned off = (unsigned)((h * a.W + w) * a.Cin) * 4u + x_lane;
+            if constexpr (ZP) off = ((unsigned)hr < (unsigned)a.H && (unsigned)wr < (unsigned)a.W) ? off : 0x80000000u;
             pv[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, off, img, 0));
         }
     };
@@ -1305,9 +1330,10 @@ bool x3_ok(int B, int H, int W, int Cin, int N, int K) {
            !(N % 4);
 }
 
-template <int KS, int BN, int WM, int WN, int TM, int TN, int DBG = 0, int PB = 2, int S2 = 0, int KSP = 1, int NPL = 3, int RING = 0>
+template <int KS, int BN, int WM, int WN, int TM, int TN, int DBG = 0, int PB = 2, int S2 = 0, int KSP = 1, int NPL = 3, int RING = 0,
+          bool ZP = false>
 void x3_launch(const X3Args& a, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL((conv_halo_x3_kernel<KS, BN, WM, WN, TM, TN, DBG, PB, S2, KSP, NPL, RING>), grid, dim3(64 * WM * WN), 0, st, a);
+    hipLaunchKernelGGL((conv_halo_x3_kernel<KS, BN, WM, WN, TM, TN, DBG, PB, S2, KSP, NPL, RING, ZP>), grid, dim3(64 * WM * WN), 0, st, a);
 }
 // 16-bit elements of the two-plane prepared filter ({s_w, 1 / s_w} follow as two floats: + 4 elements)
 size_t h2_w_elems(int rows, int kdim, int K) { return (size_t)K * K * ((kdim + CS - 1) / CS) * 2 * rows * CS; }
@@ -1565,7 +1591,7 @@ int dwc_x3_conv2d_s2(const float* x, const void* w_prepared, const float* bias, 
 
 }  // extern "C"
 
-template <int NPL>
+template <int NPL, bool ZP = false>
 static int x3_s2_ws_impl(const float* x, const void* xs, unsigned xs_epoch, const void* w_prepared, const float* bias, float* y, int B, int H,
                          int W, int Cin, int N, int rows, int act, void* ws, size_t ws_bytes, unsigned* tickets, void* stream,
                          void* ys = nullptr, unsigned ys_epoch = 0) {
@@ -1585,9 +1611,9 @@ static int x3_s2_ws_impl(const float* x, const void* xs, unsigned xs_epoch, cons
         a.status = tickets + X3_KSPLIT_TICKETS;
         const int tiles = B * a.blocks_per_img * a.tiles_n;
         a.split_from = (int)x3_ksplit_from(tiles, 4 * (Cin / CS));
-        x3_launch<2, 64, 4, 1, 2, 2, 0, 1, 1, 2, NPL>(a, dim3(2 * tiles - a.split_from), (hipStream_t)stream);
+        x3_launch<2, 64, 4, 1, 2, 2, 0, 1, 1, 2, NPL, 0, ZP>(a, dim3(2 * tiles - a.split_from), (hipStream_t)stream);
     } else {
-        x3_launch<2, 64, 4, 1, 2, 2, 0, 1, 1, 1, NPL>(a, dim3(B * a.blocks_per_img * a.tiles_n), (hipStream_t)stream);
+        x3_launch<2, 64, 4, 1, 2, 2, 0, 1, 1, 1, NPL, 0, ZP>(a, dim3(B * a.blocks_per_img * a.tiles_n), (hipStream_t)stream);
     }
     DWC_LAUNCH_CHECK();
     return DWC_OK;
@@ -1627,6 +1653,18 @@ int dwc_h2_conv2d_s2_ws(const float* x, const void* x_amax, unsigned x_epoch, co
                         void* y_amax, unsigned y_epoch, int B, int H, int W, int Cin, int N, int rows, int act, void* ws, size_t ws_bytes,
                         unsigned* tickets, void* stream) {
     return x3_s2_ws_impl<2>(x, x_amax, x_epoch, w_prepared, bias, y, B, H, W, Cin, N, rows, act, ws, ws_bytes, tickets, stream, y_amax, y_epoch);
+}
+/* the same forwards of the ZERO-padded 4x4 stride-2 pad-1 convolution: shapes (dwc_x3_conv2d_s2_ok), prepared weights, contraction
+ * split and scratch of dwc_x3_conv2d_s2_ws / dwc_h2_conv2d_s2_ws */
+int dwc_x3_conv2d_s2_ws_zeropad(const float* x, const void* w_prepared, const float* bias, float* y, int B, int H, int W, int Cin, int N,
+                                int rows, int act, void* ws, size_t ws_bytes, unsigned* tickets, void* stream) {
+    return x3_s2_ws_impl<3, true>(x, nullptr, 0, w_prepared, bias, y, B, H, W, Cin, N, rows, act, ws, ws_bytes, tickets, stream);
+}
+int dwc_h2_conv2d_s2_ws_zeropad(const float* x, const void* x_amax, unsigned x_epoch, const void* w_prepared, const float* bias, float* y,
+                                void* y_amax, unsigned y_epoch, int B, int H, int W, int Cin, int N, int rows, int act, void* ws,
+                                size_t ws_bytes, unsigned* tickets, void* stream) {
+    return x3_s2_ws_impl<2, true>(x, x_amax, x_epoch, w_prepared, bias, y, B, H, W, Cin, N, rows, act, ws, ws_bytes, tickets, stream, y_amax,
+                                  y_epoch);
 }
 
 /* INTERIOR of the data gradient of the same layers (conv_halo_x3_kernel, S2 == 2): dy:[B,H/2,W/2,Cout] fp32 -> the H x W pixels
@@ -1673,11 +1711,13 @@ size_t dwc_x3_conv2d_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout, int 
  * W % 32 == 0; Cin and Cout multiples of 64) - use dwc_conv2d_bwd_weight. */
 }  // extern "C"
 
-template <int NPL>
+template <int NPL, bool ZP = false>
 static int x3_wgrad_impl(const float* x, const void* xs, unsigned xs_epoch, const float* dy, const void* dys, unsigned dys_epoch, float* dw_oihw,
                          int B, int H, int W, int Cin, int Cout, int K, int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream) {
     const int bn = x3_wgrad_bn(B, H, W, Cin, Cout, K);
     if (!x || !dy || !dw_oihw || !bn || cin_real > Cin || cout_real > Cout || (NPL == 2 && (!xs || !dys))) return DWC_EINVAL;
+    // (the zero rule is the offset 2^31: it must lie past the end of x)
+    if (ZP && (size_t)B * H * W * Cin * 4 >= 0x80000000ull) return DWC_EINVAL;
     int splits, ups;
     x3_wgrad_plan(B, H, W, Cin, Cout, K, bn, NPL, &splits, &ups);
     const int halves = bn == 128 ? 1 : 2;
@@ -1698,12 +1738,12 @@ static int x3_wgrad_impl(const float* x, const void* xs, unsigned xs_epoch, cons
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(a.roles * splits);
     if (K == 4) {
-        if (bn == 128) hipLaunchKernelGGL((wgrad_x3_kernel<4, 128, 64, 2, NPL>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((wgrad_x3_kernel<4, 64, 64, 2, NPL>), grid, dim3(512), 0, st, a);
-    } else if (K == 3 && bn == 128) hipLaunchKernelGGL((wgrad_x3_kernel<3, 128, 64, 2, NPL>), grid, dim3(512), 0, st, a);
-    else if (K == 3) hipLaunchKernelGGL((wgrad_x3_kernel<3, 64, 64, 2, NPL>), grid, dim3(512), 0, st, a);
-    else if (bn == 128) hipLaunchKernelGGL((wgrad_x3_kernel<5, 128, 64, 2, NPL>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((wgrad_x3_kernel<5, 64, 64, 2, NPL>), grid, dim3(512), 0, st, a);
+        if (bn == 128) hipLaunchKernelGGL((wgrad_x3_kernel<4, 128, 64, 2, NPL, ZP>), grid, dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((wgrad_x3_kernel<4, 64, 64, 2, NPL, ZP>), grid, dim3(512), 0, st, a);
+    } else if (K == 3 && bn == 128) hipLaunchKernelGGL((wgrad_x3_kernel<3, 128, 64, 2, NPL, ZP>), grid, dim3(512), 0, st, a);
+    else if (K == 3) hipLaunchKernelGGL((wgrad_x3_kernel<3, 64, 64, 2, NPL, ZP>), grid, dim3(512), 0, st, a);
+    else if (bn == 128) hipLaunchKernelGGL((wgrad_x3_kernel<5, 128, 64, 2, NPL, ZP>), grid, dim3(512), 0, st, a);
+    else hipLaunchKernelGGL((wgrad_x3_kernel<5, 64, 64, 2, NPL, ZP>), grid, dim3(512), 0, st, a);
     DWC_LAUNCH_CHECK();
     const size_t total = (size_t)K * K * Cin * Cout;
     hipLaunchKernelGGL(x3_wgrad_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const float*)ws, dw_oihw, splits * halves,
@@ -1723,6 +1763,18 @@ int dwc_h2_conv2d_wgrad(const float* x, const void* x_amax, unsigned x_epoch, co
                         float* dw_oihw, int B, int H, int W, int Cin, int Cout, int K, int cin_real, int cout_real, void* ws, size_t ws_bytes,
                         void* stream) {
     return x3_wgrad_impl<2>(x, x_amax, x_epoch, dy, dy_amax, dy_epoch, dw_oihw, B, H, W, Cin, Cout, K, cin_real, cout_real, ws, ws_bytes, stream);
+}
+/* the same weight gradients of the ZERO-padded convolution (pad (K-1)/2 at stride 1, pad 1 for the 4x4 stride-2 layer): shapes, plan
+ * and scratch of dwc_x3_conv2d_wgrad / dwc_h2_conv2d_wgrad; x of less than 2 GiB */
+int dwc_x3_conv2d_wgrad_zeropad(const float* x, const float* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int K,
+                                int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream) {
+    return x3_wgrad_impl<3, true>(x, nullptr, 0, dy, nullptr, 0, dw_oihw, B, H, W, Cin, Cout, K, cin_real, cout_real, ws, ws_bytes, stream);
+}
+int dwc_h2_conv2d_wgrad_zeropad(const float* x, const void* x_amax, unsigned x_epoch, const float* dy, const void* dy_amax,
+                                unsigned dy_epoch, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int K, int cin_real,
+                                int cout_real, void* ws, size_t ws_bytes, void* stream) {
+    return x3_wgrad_impl<2, true>(x, x_amax, x_epoch, dy, dy_amax, dy_epoch, dw_oihw, B, H, W, Cin, Cout, K, cin_real, cout_real, ws, ws_bytes,
+                                  stream);
 }
 
 }  // extern "C"

@@ -399,7 +399,9 @@ __global__ __launch_bounds__(256) void conv_gemm_strips_kernel(StripSet ss) {
 // X3: the contraction over pixels as exact bf16 split products (see conv_gemm_body): both operands are read from the unchanged
 // fp32 LDS tiles -- eight pixels of one k / n column per lane and 16-deep step, the same ds_read_b32 count as the fp32 MFMA path --
 // and split in registers.
-template <int BN, int WM, int WN, int TM, int TN, bool X3 = false>
+// ZP: the zero rule (weight gradient of a zero-padded convolution): an A^T row whose gathered pixel lies outside the image comes
+// from the zero page, as in conv_gemm_body.  A compile-time rule: the reflect instantiations are the instructions they were.
+template <int BN, int WM, int WN, int TM, int TN, bool X3 = false, bool ZP = false>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(Gather g, const float* __restrict__ dy, int N, float* __restrict__ slab,
                                                          int m_chunk, int splits_per_class = 0, size_t src_class_stride = 0,
                                                          size_t dy_class_stride = 0) {
@@ -464,9 +466,17 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(Gather g, const float* 
                 oh = rem / g.OW;
                 ow = rem - oh * g.OW;
             }
-            const int h = reflect_idx(oh * g.mul_h + dh, g.SH);
-            const int w = reflect_idx(ow * g.mul_w + dw, g.SW);
-            const float* s = (const float*)g.src + (((n * g.SH + h) * g.SW + w) << g.logSC) + ci;
+            const float* s;
+            if constexpr (ZP) {
+                const int h = oh * g.mul_h + dh, w = ow * g.mul_w + dw;
+                const bool inb = (unsigned)h < (unsigned)g.SH && (unsigned)w < (unsigned)g.SW;
+                const int hc = min(max(h, 0), g.SH - 1), wc = min(max(w, 0), g.SW - 1);
+                s = inb ? (const float*)g.src + (((n * g.SH + hc) * g.SW + wc) << g.logSC) + ci : g_zero_page;
+            } else {
+                const int h = reflect_idx(oh * g.mul_h + dh, g.SH);
+                const int w = reflect_idx(ow * g.mul_w + dw, g.SW);
+                s = (const float*)g.src + (((n * g.SH + h) * g.SW + w) << g.logSC) + ci;
+            }
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)s,
                                              (__attribute__((address_space(3))) void*)(la + i * 8 * 128), 16, 0, 0);
         }
@@ -637,6 +647,7 @@ struct Im2colF32 {
     static constexpr int BK = ::BK;
     static constexpr int MIN_LOG_C = 2;             // a 16-byte staging chunk is 4 channels
     static constexpr int CH_MASK = 3;
+    static constexpr bool ZERO_BY_OFFSET = false;   // out-of-image rows come from g_zero_page
     static constexpr bool HALF_STRIPS = false;      // only the 64-row strip tile exists (strip_bm)
     static constexpr int WGRAD_SLAB_ROWS = 32;
     static constexpr int IMAGE_PX = 8;              // NHWC4 images: 8 pixels x 4 planes per GEMM row
@@ -685,29 +696,27 @@ struct Im2colF32 {
         return DWC_OK;
     }
 
+    template <bool X3, bool ZP>
+    static void wgrad_kernels(const Gather& g, const float* dy, int Cout, float* slab, int splits, int chunk, hipStream_t st) {
+        const int tk = (g.K + 127) / 128, bn = wgrad_bn(Cout);
+        if (bn == 128)
+            hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2, X3, ZP>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
+                               Cout, slab, chunk);
+        else if (bn == 64)
+            hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1, X3, ZP>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+        else
+            hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1, X3, ZP>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
+    }
+
     static int wgrad_launch(const FwdGeom& f, const float* dy, float* dw_oihw, int Cin, int Cout, int KHW, int cin_real, int cout_real,
                             void* ws, size_t ws_bytes, hipStream_t st) {
         const Gather& g = f.g;
         int splits, chunk;
         if (!ws || ws_bytes < wgrad_ws_bytes(g.M, g.K, Cout, WGRAD_SLAB_ROWS, &splits, &chunk)) return DWC_EWORKSPACE;
         float* slab = (float*)ws;
-        const int tk = (g.K + 127) / 128, bn = wgrad_bn(Cout);
-        if (wgrad_x3_on()) {
-            if (bn == 128)
-                hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2, true>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
-                                   Cout, slab, chunk);
-            else if (bn == 64)
-                hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-            else
-                hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1, true>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-        } else if (bn == 128) {
-            hipLaunchKernelGGL((conv_wgrad_kernel<128, 2, 2, 2, 2>), dim3(tk, (Cout + 127) / 128, splits), dim3(256), 0, st, g, dy,
-                               Cout, slab, chunk);
-        } else if (bn == 64) {
-            hipLaunchKernelGGL((conv_wgrad_kernel<64, 2, 2, 2, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-        } else {
-            hipLaunchKernelGGL((conv_wgrad_kernel<32, 4, 1, 1, 1>), dim3(tk, 1, splits), dim3(256), 0, st, g, dy, Cout, slab, chunk);
-        }
+        // (Gather::reflect == 0: the zero-rule instantiations, conv2d_bwd_weight_zeropad)
+        if (wgrad_x3_on()) g.reflect ? wgrad_kernels<true, false>(g, dy, Cout, slab, splits, chunk, st) : wgrad_kernels<true, true>(g, dy, Cout, slab, splits, chunk, st);
+        else g.reflect ? wgrad_kernels<false, false>(g, dy, Cout, slab, splits, chunk, st) : wgrad_kernels<false, true>(g, dy, Cout, slab, splits, chunk, st);
         DWC_LAUNCH_CHECK();
         wgrad_reduce(slab, dw_oihw, splits, g.K, Cout, Cin, KHW, cin_real, cout_real, st);
         DWC_LAUNCH_CHECK();

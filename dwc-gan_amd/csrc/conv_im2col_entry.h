@@ -10,6 +10,8 @@
 //                      (in fp32 this is no restriction of its own: every `& CH_MASK` check below repeats what conv_args_ok, bwd_geom,
 //                      zeropad_dgrad_geom and fwd_geom_ex already reject with `& 3`, so the fp32 return codes are those of the geometry
 //                      builders alone; only bf16's 7 rejects anything they accept)
+//   ZERO_BY_OFFSET     the zero rule of the weight-gradient / crop entries is an offset past a 2 GiB buffer descriptor (false / true):
+//                      those entries then refuse larger gathered tensors
 //   HALF_STRIPS        the `half` flag of strip_bm: the 128-row strip tile exists (false / true)
 //   WGRAD_SLAB_ROWS    pixels per slab of the weight-gradient kernel (32 / 64)
 //   IMAGE_PX           pixels per GEMM row of image_dgrad_geom (8 x 4 planes / 4 x 8 planes)
@@ -19,8 +21,8 @@
 //   fold_image         the whole-image reflect-pad adjoint
 //   band_args_bad      the argument checks of reflect_pad_adjoint_band in which the precisions differ
 // Return codes are the same for both precisions unless a policy member says otherwise.  Three checks do NOT follow CH_MASK, in either
-// precision: reflect_pad_adjoint accepts any multiple of 4 channels; of the *_ws_bytes functions only bwd_data_zeropad_ws_bytes
-// applies CH_MASK (the others answer for every count their geometry builder takes, multiples of 4); and zeropad_dgrad_geom /
+// precision: reflect_pad_adjoint accepts any multiple of 4 channels; of the *_ws_bytes functions only bwd_data_zeropad_ws_bytes and
+// bwd_data_crop_ws_bytes apply CH_MASK (the others answer for every count their geometry builder takes, multiples of 4); and zeropad_dgrad_geom /
 // same_dgrad_geom take no min_log_c (the bf16 entry points rely on CH_MASK there).
 #pragma once
 #include "conv_fold.h"
@@ -171,6 +173,52 @@ int im2col_bwd_data_fold(const void* dy, const void* w_dgrad, void* dxp, void* d
     return fold_band((const typename P::T*)dxp, (typename P::T*)dx, B, H, W, Cin, pad, st);
 }
 
+// Data gradient of a ZERO-padded convolution at any stride and pad bwd_geom takes: the adjoint of zero padding is a crop, so the
+// interior of the gradient of the padded image IS dx.  One scratch arena, ws = [padded gradient image, rounded up to 256 bytes]
+// [split-K partials].  Where the GEMM runs unsplit Scatter::crop writes the interior straight into dx (the border ring lands in the
+// scratch image and is dropped: the `direct` branch of bwd_data_fold without the band fold); a split plan reduces into the scratch
+// image and a copy crops it.  pad == 0: no scratch image, the GEMM writes dx.
+template <class P>
+size_t im2col_bwd_data_crop_image_bytes(int B, int H, int W, int Cin, int pad) {
+    if (pad == 0) return 0;
+    return ((size_t)B * (H + 2 * pad) * (W + 2 * pad) * Cin * sizeof(typename P::T) + 255) / 256 * 256;
+}
+
+template <class P>
+size_t im2col_bwd_data_crop_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+    BwdGeom f;
+    if ((Cin & P::CH_MASK) || !bwd_geom(nullptr, nullptr, B, H, W, Cin, Cout, KH, KW, stride, pad, &f, P::BK, P::MIN_LOG_C)) return 0;
+    return im2col_bwd_data_crop_image_bytes<P>(B, H, W, Cin, pad) +
+           gemm_ws_bytes(im2col_plan<P>(f.g.M, Cin, f.g.K, f.classes), f.dst_elems);
+}
+
+template <class P>
+int im2col_bwd_data_crop(const void* dy, const void* w_dgrad, void* dx, int B, int H, int W, int Cin, int Cout, int KH, int KW,
+                         int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
+    BwdGeom f;
+    if (!dy || !w_dgrad || !dx || (Cin & P::CH_MASK) ||
+        !bwd_geom(dy, dx, B, H, W, Cin, Cout, KH, KW, stride, pad, &f, P::BK, P::MIN_LOG_C))
+        return DWC_EINVAL;
+    // (the zero rule of the bf16 gather is an offset past the descriptor, conv_bf16.hip OOB; the fp32 gather reads the zero page)
+    if (P::ZERO_BY_OFFSET && (size_t)B * f.g.SH * f.g.SW * Cout * sizeof(typename P::T) >= 0x80000000ull) return DWC_EINVAL;
+    const size_t image_bytes = im2col_bwd_data_crop_image_bytes<P>(B, H, W, Cin, pad);
+    const Plan plan = im2col_plan<P>(f.g.M, f.o.N, f.g.K, f.classes);
+    const size_t part_bytes = gemm_ws_bytes(plan, f.dst_elems);
+    if (image_bytes + part_bytes && (!ws || ws_bytes < image_bytes + part_bytes)) return DWC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const bool direct = plan.splits == 1;
+    if (pad > 0) {
+        f.o.dst = ws;
+        if (direct) {
+            f.o.crop = pad; f.o.IH = H; f.o.IW = W; f.o.inner = dx;
+        }
+    }
+    const int rc = P::launch_gemm(f.g, (const typename P::T*)w_dgrad, f.wcs, f.classes, f.o, nullptr, DWC_ACT_NONE, f.dst_elems,
+                                  part_bytes ? (char*)ws + image_bytes : nullptr, part_bytes, st);
+    if (rc != DWC_OK || pad == 0 || direct) return rc;
+    return crop_image((const typename P::T*)ws, (typename P::T*)dx, B, H, W, Cin / 4, pad, st);
+}
+
 // Data gradient of a stride-1 "same" convolution in one call (same_dgrad_geom): the interior on the H x W grid straight into dx, the
 // border ring as four strips of fp32 partials at the head of ws, folded onto dx.
 template <class P>
@@ -249,12 +297,20 @@ size_t im2col_bwd_weight_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH
     return wgrad_ws_bytes(B * Ho * Wo, KH * KW * Cin, Cout, P::WGRAD_SLAB_ROWS, &splits, &chunk);
 }
 
+// reflect == 0: the weight gradient of a zero-padded convolution -- the same kernel, A^T rows outside the image read as zeros
+// (wgrad_launch picks the zero-rule instantiation by Gather::reflect).  Same plan, same scratch.
 template <class P>
 int im2col_bwd_weight(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
-                      int pad, int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream) {
+                      int pad, int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream, int reflect = 1) {
     FwdGeom f;
     if (!fwd_geom(x, nullptr, B, H, W, Cin, Cout, KH, KW, stride, pad, &f, P::MIN_LOG_C)) return DWC_EINVAL;
     if (cin_real > Cin || cout_real > Cout || (Cout & P::CH_MASK)) return DWC_EINVAL;
+    if (!reflect) {
+        // (the zero rule of the bf16 gather is an offset past the descriptor, conv_bf16.hip OOB; the fp32 gather reads the zero page)
+        if (!x || !dy || !dw_oihw) return DWC_EINVAL;
+        if (P::ZERO_BY_OFFSET && (size_t)B * H * W * Cin * sizeof(typename P::T) >= 0x80000000ull) return DWC_EINVAL;
+        f.g.reflect = 0;
+    }
     return P::wgrad_launch(f, (const typename P::T*)dy, dw_oihw, Cin, Cout, KH * KW, cin_real, cout_real, ws, ws_bytes,
                            (hipStream_t)stream);
 }
@@ -382,6 +438,20 @@ int im2col_bwd_weight_ex(const void* x, const void* dy, float* dw_oihw, int B, i
     int NAME(conv2d_bwd_weight)(const X* x, const X* dy, float* dw, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,  \
                                 int pad, int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream) {                         \
         return im2col_bwd_weight<P>(x, dy, dw, B, H, W, Cin, Cout, KH, KW, stride, pad, cin_real, cout_real, ws, ws_bytes, stream);      \
+    }                                                                                                                                    \
+    size_t NAME(conv2d_bwd_weight_zeropad_ws_bytes)(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {       \
+        return im2col_bwd_weight_ws_bytes<P>(B, H, W, Cin, Cout, KH, KW, stride, pad);                                                   \
+    }                                                                                                                                    \
+    int NAME(conv2d_bwd_weight_zeropad)(const X* x, const X* dy, float* dw, int B, int H, int W, int Cin, int Cout, int KH, int KW,      \
+                                        int stride, int pad, int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream) {     \
+        return im2col_bwd_weight<P>(x, dy, dw, B, H, W, Cin, Cout, KH, KW, stride, pad, cin_real, cout_real, ws, ws_bytes, stream, 0);   \
+    }                                                                                                                                    \
+    size_t NAME(conv2d_bwd_data_crop_ws_bytes)(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {            \
+        return im2col_bwd_data_crop_ws_bytes<P>(B, H, W, Cin, Cout, KH, KW, stride, pad);                                                \
+    }                                                                                                                                    \
+    int NAME(conv2d_bwd_data_crop)(const X* dy, const X* w, X* dx, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,   \
+                                   int pad, void* ws, size_t ws_bytes, void* stream) {                                                   \
+        return im2col_bwd_data_crop<P>(dy, w, dx, B, H, W, Cin, Cout, KH, KW, stride, pad, ws, ws_bytes, stream);                        \
     }                                                                                                                                    \
     size_t NAME(conv2d_bwd_weight_ex_ws_bytes)(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride_h, int stride_w,       \
                                                int pad_h, int pad_w) {                                                                   \

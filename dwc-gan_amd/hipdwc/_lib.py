@@ -226,6 +226,21 @@ SIGNATURES = {
     "dwc_conv2d_bwd_weight_plan": (c_int, [c_int] * 9 + [c_fp]),
     "dwc_bf16_conv2d_fwd_plan": (c_int, [c_int] * 9 + [c_fp]),
     "dwc_bf16_conv2d_bwd_weight_plan": (c_int, [c_int] * 9 + [c_fp]),
+    # ---- zero-padded convolutions with trainable weights (pad_type 'zero'; additive in ABI 11) ----
+    "dwc_conv2d_bwd_weight_zeropad_ws_bytes": (c_sz, [c_int] * 9),
+    "dwc_conv2d_bwd_weight_zeropad": (c_int, [c_fp, c_fp, c_fp] + [c_int] * 11 + [c_fp, c_sz, c_fp]),
+    "dwc_conv2d_bwd_data_crop_ws_bytes": (c_sz, [c_int] * 9),
+    "dwc_conv2d_bwd_data_crop": (c_int, [c_fp, c_fp, c_fp] + [c_int] * 9 + [c_fp, c_sz, c_fp]),
+    "dwc_bf16_conv2d_bwd_weight_zeropad_ws_bytes": (c_sz, [c_int] * 9),
+    "dwc_bf16_conv2d_bwd_weight_zeropad": (c_int, [c_fp, c_fp, c_fp] + [c_int] * 11 + [c_fp, c_sz, c_fp]),
+    "dwc_bf16_conv2d_bwd_data_crop_ws_bytes": (c_sz, [c_int] * 9),
+    "dwc_bf16_conv2d_bwd_data_crop": (c_int, [c_fp, c_fp, c_fp] + [c_int] * 9 + [c_fp, c_sz, c_fp]),
+    "dwc_x3_conv2d_wgrad_zeropad": (c_int, [c_fp, c_fp, c_fp] + [c_int] * 8 + [c_fp, c_sz, c_fp]),
+    "dwc_h2_conv2d_wgrad_zeropad": (c_int, [c_fp, c_fp, c_u, c_fp, c_fp, c_u, c_fp] + [c_int] * 8 + [c_fp, c_sz, c_fp]),
+    "dwc_bf16_conv2d_wgrad_halo_zeropad": (c_int, [c_fp, c_fp, c_fp] + [c_int] * 8 + [c_fp, c_sz, c_fp]),
+    "dwc_x3_conv2d_s2_ws_zeropad": (c_int, [c_fp] * 4 + [c_int] * 7 + [c_fp, c_sz, c_fp, c_fp]),
+    "dwc_h2_conv2d_s2_ws_zeropad": (c_int, [c_fp, c_fp, c_u, c_fp, c_fp, c_fp, c_fp, c_u] + [c_int] * 7 + [c_fp, c_sz, c_fp, c_fp]),
+    "dwc_bf16_conv2d_s2_halo_zeropad": (c_int, [c_fp, c_fp, c_fp, c_fp] + [c_int] * 6 + [c_fp]),
 }
 
 ABI_VERSION = 11             # DWC_ABI_VERSION of include/dwcgan_hip.h

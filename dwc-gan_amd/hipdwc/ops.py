@@ -602,6 +602,7 @@ S2DGRAD = int(os.environ.get("DWC_S2_DGRAD_HALO", "1"))   # stride-2 4x4 DATA GR
 X3_WGRAD_HALO3 = int(os.environ.get("DWC_X3_WGRAD_HALO3", "1"))   # 0: 3x3 weight gradients on the im2col kernel (split-product inner product)
 PINNED_STAGE = int(os.environ.get("DWC_PINNED_STAGE", "1"))        # small host->device tables through pinned staging (0: pageable copies, which wait for the stream)
 ZERO_GRAD_BY_FLAG = int(os.environ.get("DWC_ZERO_GRAD_FLAG", "1"))   # biases whose gradient is identically zero: flagged, not filled (0: torch.zeros per use)
+ZERO_PAD_HIP = int(os.environ.get("DWC_ZERO_PAD_HIP", "1"))   # Conv2dBlock pad_type 'zero': the rule inside the kernels (0: F.pad in front of the unpadded convolution, stride 1 only)
 RING_FUSED = int(os.environ.get("DWC_RING_FUSED", "1"))   # stride-1 data gradients: border ring inside the halo launch (0: strip GEMM + fold launches)
 # gradient / R1 penalties of the D step on the closed-form second derivative over the HIP convolutions (hipdwc.penalty) where the
 # discriminator allows it (MsImageDis.penalty_hip_ok); 0: always torch's double backward (MsImageDis.forward_src_scale0_torch).
@@ -798,11 +799,17 @@ def ksplit_status_poll(wait=False):
 
 
 class _Conv2d(torch.autograd.Function):
-    """act(conv(reflect_pad(x)) + b).  Output has Cout rounded up to a multiple of 4 (fp32) / 8 (bf16); its dtype is x's.
-    ``owner``: the parameter(s) ``w`` is derived from when ``w`` is a fresh tensor on every call (prepared-weight cache)."""
+    """act(conv(pad(x)) + b), the padding rule inside the kernels' gather.  Output has Cout rounded up to a multiple of 4 (fp32) /
+    8 (bf16); its dtype is x's.
+    ``owner``: the parameter(s) ``w`` is derived from when ``w`` is a fresh tensor on every call (prepared-weight cache).
+    ``zero``: zero padding instead of reflect padding (Conv2dBlock pad_type 'zero').  The same kernel families by the same size rules
+    and the same prepared layouts where the kernel takes the rule (stride-1 and stride-2 halo forwards, stem forward, the halo weight
+    gradients, every halo data gradient: the adjoint of zero padding is a crop, so the interior launch is the whole gradient -- no
+    ring, strips or fold); the 7x7 layers' gradients and every shape no halo kernel takes run on the im2col zero-rule entries
+    (dwc_conv2d_fwd_zeropad / _bwd_weight_zeropad / _bwd_data_crop).  Absmax slots, bias_grad, token and nograd as under reflect."""
 
     @staticmethod
-    def forward(ctx, x, w, b, stride, pad, act, bias_grad=True, owner=None, token=None, nograd=False):
+    def forward(ctx, x, w, b, stride, pad, act, bias_grad=True, owner=None, token=None, nograd=False, zero=False):
         _require_device(x)
         lib = _lib.load()
         x = cl(x)
@@ -815,6 +822,10 @@ class _Conv2d(torch.autograd.Function):
         ctx.bias_grad = bias_grad
         ctx.zero_flag = bool(b is not None and getattr(b, "_dwc_zero_grad", False))
         ctx.owner = owner
+        zero = bool(zero and pad > 0)                     # (nothing gathered outside the image: the rules coincide)
+        ctx.zero = zero
+        refl = 0 if zero else 1
+        z = "_zeropad" if zero else ""              # the stride-2 halo forwards: the zero-rule twins of the same entries
         cop = _padc(Cout, x.dtype)
         Ho = (H + 2 * pad - KH) // stride + 1
         Wo = (W + 2 * pad - KW) // stride + 1
@@ -844,7 +855,7 @@ class _Conv2d(torch.autograd.Function):
             x_amax = amax_of(x)
             ya, yep = out_amax(y)
             _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_same_add_ws(
-                x.data_ptr(), x_amax[0], x_amax[1], w_h2.data_ptr(), _p(bias), None, y.data_ptr(), ya, yep, B, H, W, Cx, cop, cop, KH, act, 1,
+                x.data_ptr(), x_amax[0], x_amax[1], w_h2.data_ptr(), _p(bias), None, y.data_ptr(), ya, yep, B, H, W, Cx, cop, cop, KH, act, refl,
                 _p(ks_ws), ks_n, ks_t, st), detail="fwd-h2 B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride), exec_flops=3 * flops),
                 "h2_conv2d_same")
             set_amax(y, ya, yep)
@@ -852,14 +863,14 @@ class _Conv2d(torch.autograd.Function):
             w_x3 = _prepped(w, "x3_fwd", cop, Cx, 1, owner)
             ks_ws, ks_n, ks_t = _x3_ksplit(lib, x.device, B, H, W, Cx, cop, KH, 1)
             _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_same_add_ws(
-                x.data_ptr(), w_x3.data_ptr(), _p(bias), None, y.data_ptr(), B, H, W, Cx, cop, cop, KH, act, 1, _p(ks_ws), ks_n, ks_t, st),
+                x.data_ptr(), w_x3.data_ptr(), _p(bias), None, y.data_ptr(), B, H, W, Cx, cop, cop, KH, act, refl, _p(ks_ws), ks_n, ks_t, st),
                 detail="fwd-x3 B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride), exec_flops=6 * flops), "x3_conv2d_same")
         elif use_x3s2 and h2_fits(x):
             w_h2 = _prepped(w, "h2_fwd", cop, Cx, 1, owner)
             ks_ws, ks_n, ks_t = _x3_ksplit(lib, x.device, B, H, W, Cx, cop, KH, 2)
             x_amax = amax_of(x)
             ya, yep = out_amax(y)
-            _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_s2_ws(
+            _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: getattr(lib, "dwc_h2_conv2d_s2_ws" + z)(
                 x.data_ptr(), x_amax[0], x_amax[1], w_h2.data_ptr(), _p(bias), y.data_ptr(), ya, yep, B, H, W, Cx, cop, cop, act, _p(ks_ws), ks_n,
                 ks_t, st), detail="fwd-h2s2 B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride), exec_flops=3 * flops), "h2_conv2d_s2")
             set_amax(y, ya, yep)
@@ -867,7 +878,7 @@ class _Conv2d(torch.autograd.Function):
             # stride-2 4x4 layers, fp32: split products, 2x2 taps per input-pixel parity, space-to-depth in the patch gather
             w_x3 = _prepped(w, "x3_fwd", cop, Cx, 1, owner)
             ks_ws, ks_n, ks_t = _x3_ksplit(lib, x.device, B, H, W, Cx, cop, KH, 2)
-            _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_s2_ws(
+            _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: getattr(lib, "dwc_x3_conv2d_s2_ws" + z)(
                 x.data_ptr(), w_x3.data_ptr(), _p(bias), y.data_ptr(), B, H, W, Cx, cop, cop, act, _p(ks_ws), ks_n, ks_t, st),
                 detail="fwd-x3s2 B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride), exec_flops=6 * flops), "x3_conv2d_s2")
         elif use_stem_x3:
@@ -875,7 +886,7 @@ class _Conv2d(torch.autograd.Function):
             w_st = _prepped(w, "stem_steps_x3", cop, Cx, 1, owner)
             ya, yep = out_amax(y)                     # (the stride-2 layer behind the stem is a two-plane kernel: it wants y's absmax)
             _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_stem_amax(
-                x.data_ptr(), w_st.data_ptr(), _p(bias), y.data_ptr(), ya, yep, B, H, W, H, W, KH, -pad, act, 1, st),
+                x.data_ptr(), w_st.data_ptr(), _p(bias), y.data_ptr(), ya, yep, B, H, W, H, W, KH, -pad, act, refl, st),
                 detail="fwd-stem-x3 B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride), exec_flops=6 * flops), "x3_conv2d_stem")
             if ya is not None:
                 set_amax(y, ya, yep)
@@ -883,23 +894,23 @@ class _Conv2d(torch.autograd.Function):
             # 7x7 stem on an NHWC8 image: filter resident in LDS, persistent workgroups (csrc/conv_narrow_bf16.hip)
             w_st = _prepped(w, "stem_steps", cop, Cx, 1, owner, True)
             _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_stem(
-                x.data_ptr(), w_st.data_ptr(), _p(bias), y.data_ptr(), B, H, W, H, W, KH, -pad, act, 1, st),
+                x.data_ptr(), w_st.data_ptr(), _p(bias), y.data_ptr(), B, H, W, H, W, KH, -pad, act, refl, st),
                 detail="fwd-stem B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)), "conv2d_stem")
         elif (half and HALO and S2HALO and stride == 2 and KH == 4 and KW == 4 and pad == 1
               and lib.dwc_bf16_conv2d_s2_halo_ok(B, H, W, Cx, cop)):
             # stride-2 4x4 layers on the bf16 path: 2x2 taps over the space-to-depth image, space-to-depth done by the loader
-            _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_s2_halo(
+            _lib.check(_timed("conv_gemm_kernel", flops, lambda: getattr(lib, "dwc_bf16_conv2d_s2_halo" + z)(
                 x.data_ptr(), w_hwio.data_ptr(), _p(bias), y.data_ptr(), B, H, W, Cx, cop, act, st),
                 detail="fwd-s2halo B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)), "conv2d_s2_halo")
         elif half and HALO and stride == 1 and KH == KW and 2 * pad == KH - 1 and lib.dwc_bf16_conv2d_same_halo_ok(B, H, W, Cx, cop, KH):
             # stride-1 "same" 3x3 / 5x5 layers on the bf16 path: halo-tiled kernel (patch staged once per channel slab)
             _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_same_halo(
-                x.data_ptr(), w_hwio.data_ptr(), _p(bias), y.data_ptr(), B, H, W, Cx, cop, KH, act, 1, st),
+                x.data_ptr(), w_hwio.data_ptr(), _p(bias), y.data_ptr(), B, H, W, Cx, cop, KH, act, refl, st),
                 detail="fwd-halo B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)), "conv2d_same_halo")
         else:
             nws = _fn(lib, "conv2d_fwd_ws_bytes", x)(B, H, W, Cx, cop, KH, KW, stride, pad)     # split-K partials, usually 0
             wsp = workspace(nws, x.device).data_ptr() if nws else None
-            _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_fwd", x)(
+            _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_fwd_zeropad" if zero else "conv2d_fwd", x)(
                 x.data_ptr(), w_hwio.data_ptr(), _p(bias), y.data_ptr(), B, H, W, Cx, cop, KH, KW, stride, pad, act, wsp, nws,
                 st), detail="fwd B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)), "conv2d_fwd")
         ctx.save_for_backward(x, w, y if act != 0 else None)
@@ -958,17 +969,21 @@ class _Conv2d(torch.autograd.Function):
                 if g_res.shape[1] != Cx or g_res.dtype != dt or not ctx.needs_input_grad[0]:
                     raise RuntimeError("residual-gradient token: shape / dtype of the identity branch does not match the block input")
         pow2 = (cop & (cop - 1)) == 0
+        zero = ctx.zero
         if ctx.needs_input_grad[1]:
             dw = torch.empty((Cout, Cin, KH, KW), dtype=torch.float32, device=dev)
             flops = 2.0 * rows * Cout * Cin * KH * KW
             detail = "wgrad B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)
-            if half and NARROW and STEM and Cx == 8 and cop == 64 and stride == 1 and KH == 7 and KW == 7 and pad == 3 and Cout == 64:
+            # zero rule: the halo kernels' and the im2col kernel's zero-rule instantiations, by the same size rules, plans and scratch as
+            # under reflect (z); the small-K 7x7 kernels stage their patches by the reflect rule and leave those layers to im2col
+            z = "_zeropad" if zero else ""
+            if (not zero) and half and NARROW and STEM and Cx == 8 and cop == 64 and stride == 1 and KH == 7 and KW == 7 and pad == 3 and Cout == 64:
                 # 7x7 stem on an NHWC8 image: 4 taps x 8 planes per MFMA row tile (csrc/conv_narrow_bf16.hip)
                 ws = workspace(lib.dwc_bf16_conv7_smallk_wgrad_ws_bytes(B, H, W, 0), dev)
                 _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: lib.dwc_bf16_conv7_smallk_wgrad(
                     x.data_ptr(), g.data_ptr(), dw.data_ptr(), B, H, W, Cin, 0, ws.data_ptr(), ws.numel(), st),
                     scope_name=ctx.bscope, detail="wgrad-stem" + detail[5:]), "conv7_smallk_wgrad")
-            elif ((not half) and X3 and SMALLK_X3 and Cx == 4 and cop == 64 and stride == 1 and KH == 7 and KW == 7 and pad == 3
+            elif ((not zero) and (not half) and X3 and SMALLK_X3 and Cx == 4 and cop == 64 and stride == 1 and KH == 7 and KW == 7 and pad == 3
                   and Cout == 64):
                 # fp32 7x7 stem on an NHWC4 image: one filter row (8 taps x 4 planes) per MFMA row tile, split products
                 # (csrc/conv_narrow_x3.hip smallk_wgrad_x3_kernel)
@@ -978,34 +993,40 @@ class _Conv2d(torch.autograd.Function):
                     scope_name=ctx.bscope, detail="wgrad-stem-x3" + detail[5:], exec_flops=6 * flops), "x3_conv7_smallk_wgrad")
             elif ((not half) and (_x3_use(lib, B, H, W, Cx, cop, KH, KW, stride, pad)
                                   or (X3 and X3_S2 and stride == 2 and KH == 4 and KW == 4 and pad == 1))
-                  and (KH != 3 or X3_WGRAD_HALO3)
+                  and (KH != 3 or X3_WGRAD_HALO3) and (not zero or B * H * W * Cx * 4 < (1 << 31))
                   and lib.dwc_x3_conv2d_wgrad_ws_bytes(B, H, W, Cx, cop, KH)):
                 ws = workspace(lib.dwc_x3_conv2d_wgrad_ws_bytes(B, H, W, Cx, cop, KH), dev)
                 if X3_PLANES == 2:
                     xa = amax_live(x, ctx.x_amax) or amax_of(x)          # the forward's measurement if it still stands
                     ga = amax_of(g)
-                    _lib.check(_timed("wgrad_x3_kernel+reduce", flops, lambda: lib.dwc_h2_conv2d_wgrad(
+                    _lib.check(_timed("wgrad_x3_kernel+reduce", flops, lambda: getattr(lib, "dwc_h2_conv2d_wgrad" + z)(
                         x.data_ptr(), xa[0], xa[1], g.data_ptr(), ga[0], ga[1], dw.data_ptr(), B, H, W, Cx, cop, KH, Cin, Cout, ws.data_ptr(),
-                        ws.numel(), st), scope_name=ctx.bscope, detail="wgrad-h2" + detail[5:], exec_flops=3 * flops), "h2_conv2d_wgrad")
+                        ws.numel(), st), scope_name=ctx.bscope, detail="wgrad-h2" + detail[5:], exec_flops=3 * flops), "h2_conv2d_wgrad" + z)
                 else:
-                    _lib.check(_timed("wgrad_x3_kernel+reduce", flops, lambda: lib.dwc_x3_conv2d_wgrad(
+                    _lib.check(_timed("wgrad_x3_kernel+reduce", flops, lambda: getattr(lib, "dwc_x3_conv2d_wgrad" + z)(
                         x.data_ptr(), g.data_ptr(), dw.data_ptr(), B, H, W, Cx, cop, KH, Cin, Cout, ws.data_ptr(), ws.numel(), st),
-                        scope_name=ctx.bscope, detail="wgrad-x3" + detail[5:], exec_flops=6 * flops), "x3_conv2d_wgrad")
+                        scope_name=ctx.bscope, detail="wgrad-x3" + detail[5:], exec_flops=6 * flops), "x3_conv2d_wgrad" + z)
             elif (half and WGRAD_HALO and KH == KW and ((stride == 1 and KH in (3, 5) and 2 * pad == KH - 1)
                                                          or (S2HALO and stride == 2 and KH == 4 and pad == 1))
                   and lib.dwc_bf16_conv2d_wgrad_halo_ws_bytes(B, H, W, Cx, cop, KH)):
                 ws = workspace(lib.dwc_bf16_conv2d_wgrad_halo_ws_bytes(B, H, W, Cx, cop, KH), dev)
-                _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: lib.dwc_bf16_conv2d_wgrad_halo(
+                _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: getattr(lib, "dwc_bf16_conv2d_wgrad_halo" + z)(
                     x.data_ptr(), g.data_ptr(), dw.data_ptr(), B, H, W, Cx, cop, KH, Cin, Cout, ws.data_ptr(), ws.numel(), st),
-                    scope_name=ctx.bscope, detail="wgrad-halo" + detail[5:]), "conv2d_wgrad_halo")
+                    scope_name=ctx.bscope, detail="wgrad-halo" + detail[5:]), "conv2d_wgrad_halo" + z)
             else:
                 nws = _fn(lib, "conv2d_bwd_weight_ws_bytes", x)(B, H, W, Cx, cop, KH, KW, stride, pad)
                 ws = workspace(nws, dev)
-                _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: _fn(lib, "conv2d_bwd_weight", x)(
+                _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: _fn(lib, "conv2d_bwd_weight" + z, x)(
                     x.data_ptr(), g.data_ptr(), dw.data_ptr(), B, H, W, Cx, cop, KH, KW, stride, pad, Cin, Cout, ws.data_ptr(),
-                    ws.numel(), st), scope_name=ctx.bscope, detail=detail), "conv2d_bwd_weight")
+                    ws.numel(), st), scope_name=ctx.bscope, detail=detail), "conv2d_bwd_weight" + z)
         same = stride == 1 and pad > 0 and 2 * pad == KH - 1 and KH == KW and cop >= 32 and pow2
-        if ctx.needs_input_grad[0] and Cx == image_planes(dt) and same:
+        if ctx.needs_input_grad[0] and zero:
+            dx, used = _Conv2d._zero_dgrad_halo(ctx, lib, g, g_res, w, same)      # None: no halo kernel takes the shape (below)
+            if used:
+                g_res = None                                   # consumed by the kernel's epilogue
+        if dx is not None:
+            pass
+        elif ctx.needs_input_grad[0] and (not zero) and Cx == image_planes(dt) and same:
             # gradient w.r.t. an NHWC4 / NHWC8 image (7x7 stems): 32/Cx pixels x Cx planes per GEMM row,
             # see dwc_conv2d_bwd_data_image
             dx = empty_cl(B, Cx, H, W, dev, dt)
@@ -1036,7 +1057,7 @@ class _Conv2d(torch.autograd.Function):
                     g.data_ptr(), w_img.data_ptr(), dx.data_ptr(), B, H, W, cop, KH, KW, pad, ws.data_ptr(), ws.numel(), st),
                     scope_name=ctx.bscope, detail="dgrad-image B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)),
                     "conv2d_bwd_data_image")
-        elif ctx.needs_input_grad[0] and same and min(H, W) >= 2 * pad + 2 and (not half or cop >= 64):
+        elif ctx.needs_input_grad[0] and (not zero) and same and min(H, W) >= 2 * pad + 2 and (not half or cop >= 64):
             # "same" convolutions: interior on the H x W grid straight into dx + the thin border ring (no padded image)
             w_dg = lambda: _prepped(w, "dgrad", cop, Cx, 1, owner, half).data_ptr()        # (lazily: the fused fp32 form reads neither)
             w_dg_t = lambda: _prepped(w, "dgrad_t", cop, Cx, 1, owner, half).data_ptr()     # (only the strip GEMMs of the ring read it)
@@ -1102,7 +1123,7 @@ class _Conv2d(torch.autograd.Function):
                     g.data_ptr(), w_dg(), w_dg_t(), dx.data_ptr(), B, H, W, Cx, cop, KH, KW, pad, ws.data_ptr(),
                     ws.numel(), st), scope_name=ctx.bscope, detail="dgrad B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)),
                     "conv2d_bwd_data_same")
-        elif (ctx.needs_input_grad[0] and S2DGRAD and stride == 2 and KH == 4 and KW == 4 and pad == 1
+        elif (ctx.needs_input_grad[0] and (not zero) and S2DGRAD and stride == 2 and KH == 4 and KW == 4 and pad == 1
               and 4 * B * (H // 32) * (W // 32) * (Cx // 64) >= S2DGRAD_MIN_WGS
               and ((half and HALO and lib.dwc_bf16_conv2d_s2_halo_bwd_data_ok(B, H, W, Cx, cop))
                    or ((not half) and X3 and lib.dwc_x3_conv2d_s2_bwd_data_ok(B, H, W, Cx, cop)))):
@@ -1154,12 +1175,19 @@ class _Conv2d(torch.autograd.Function):
             flops = 2.0 * rows * Cout * Cin * KH * KW
             # scratch arena: [gradient of the padded image (folded back below)] [split-K partials]
             esz = 2 if half else 4
-            pad_bytes = 0 if pad == 0 else (B * (H + 2 * pad) * (W + 2 * pad) * Cx * esz + 255) // 256 * 256
-            nws = _fn(lib, "conv2d_bwd_data_ws_bytes", x)(B, H, W, Cx, cop, KH, KW, stride, pad)
+            # (zero rule: one arena [padded gradient image][split-K partials], sized by the crop entry itself)
+            pad_bytes = 0 if pad == 0 or zero else (B * (H + 2 * pad) * (W + 2 * pad) * Cx * esz + 255) // 256 * 256
+            nws = _fn(lib, "conv2d_bwd_data_crop_ws_bytes" if zero else "conv2d_bwd_data_ws_bytes", x)(B, H, W, Cx, cop, KH, KW, stride, pad)
             base = workspace(pad_bytes + nws, dev).data_ptr() if pad_bytes + nws else 0
             target = dx.data_ptr() if pad == 0 else base
             wsp = base + pad_bytes if nws else None
-            if pad > 0 and DGRAD_FOLD and min(H, W) >= 2 * pad + 2 and Cx % (8 if half else 4) == 0:
+            if zero:
+                # the adjoint of zero padding is a crop: the scatter writes the interior of the padded gradient image into dx
+                _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data_crop", x)(
+                    g.data_ptr(), w_dg.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, KH, KW, stride, pad, wsp, nws, st),
+                    scope_name=ctx.bscope, detail="dgrad B%d %dx%d %d>%d k%d s%d zeropad" % (B, H, W, Cx, cop, KH, stride)),
+                    "conv2d_bwd_data_crop")
+            elif pad > 0 and DGRAD_FOLD and min(H, W) >= 2 * pad + 2 and Cx % (8 if half else 4) == 0:
                 # GEMM + reflect-pad adjoint in one call: interior straight into dx, only the border ring through the padded scratch
                 _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data_fold", x)(
                     g.data_ptr(), w_dg.data_ptr(), target, dx.data_ptr(), B, H, W, Cx, cop, KH, KW, stride, pad, wsp, nws, st),
@@ -1172,23 +1200,94 @@ class _Conv2d(torch.autograd.Function):
                     _lib.check(_fn(lib, "reflect_pad_adjoint", x)(target, dx.data_ptr(), B, H, W, Cx, pad, st), "reflect_pad_adjoint")
         if g_res is not None and dx is not None:               # no fused form on this path: the plain sum
             dx = dx + g_res.to(dx.dtype)
-        return dx, dw, db, None, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None, None
+
+    @staticmethod
+    def _zero_dgrad_halo(ctx, lib, g, g_res, w, same):
+        """Data gradient under the zero rule on the halo kernels: the zero-rule correlation of dY with the rotated filter on the image
+        grid -- what the reflect branches launch for the INTERIOR is the whole gradient.  Same families by the same size rules:
+        stride-1 halo (the residual-gradient add in its epilogue), stride-2 halo parity classes.  Returns (dx, whether g_res was
+        added); (None, False) where no halo kernel takes the shape: the caller runs the im2col GEMM with Scatter::crop."""
+        B, H, W, Cx, cop, KH, KW, stride, pad, act, Cin, Cout, has_b = ctx.geom
+        owner = ctx.owner
+        dt = g.dtype
+        half = dt == BF16
+        dev, st = g.device, _stream()
+        flops = 2.0 * g.shape[0] * g.shape[2] * g.shape[3] * Cout * Cin * KH * KW
+        shape = " B%d %dx%d %d>%d k%d s%d zeropad" % (B, H, W, Cx, cop, KH, stride)
+        if same and (not half) and _x3_use(lib, B, H, W, cop, Cx, KH, KW, stride, pad, free=True):
+            dx = empty_cl(B, Cx, H, W, dev, dt)
+            ws, ks_n, ks_t = _x3_ksplit(lib, dev, B, H, W, cop, Cx, KH, 1)
+            if h2_fits(g):
+                w_h2 = _prepped(w, "h2_dgrad", cop, Cx, 1, owner)
+                ga = amax_of(g)
+                _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_same_add_ws(
+                    g.data_ptr(), ga[0], ga[1], w_h2.data_ptr(), None, _p(g_res), dx.data_ptr(), None, 0, B, H, W, cop, Cx, Cx, KH, 0, 0,
+                    _p(ws), ks_n, ks_t, st), scope_name=ctx.bscope, exec_flops=3 * flops, detail="dgrad-h2" + shape),
+                    "h2_conv2d_same zeropad dgrad")
+            else:
+                w_x3 = _prepped(w, "x3_dgrad", cop, Cx, 1, owner)
+                _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_same_add_ws(
+                    g.data_ptr(), w_x3.data_ptr(), None, _p(g_res), dx.data_ptr(), B, H, W, cop, Cx, Cx, KH, 0, 0, _p(ws), ks_n,
+                    ks_t, st), scope_name=ctx.bscope, exec_flops=6 * flops, detail="dgrad-x3" + shape), "x3_conv2d_same zeropad dgrad")
+            return dx, True
+        if same and half and HALO and lib.dwc_bf16_conv2d_same_halo_ok(B, H, W, cop, Cx, KH):
+            dx = empty_cl(B, Cx, H, W, dev, dt)
+            w_dg = _prepped(w, "dgrad", cop, Cx, 1, owner, True)
+            _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_same_halo_add(
+                g.data_ptr(), w_dg.data_ptr(), None, _p(g_res), dx.data_ptr(), B, H, W, cop, Cx, KH, 0, 0, st),
+                scope_name=ctx.bscope, detail="dgrad-halo" + shape), "conv2d_same_halo zeropad dgrad")
+            return dx, True
+        if (S2DGRAD and stride == 2 and KH == 4 and KW == 4 and pad == 1
+                and 4 * B * (H // 32) * (W // 32) * (Cx // 64) >= S2DGRAD_MIN_WGS
+                and ((half and HALO and lib.dwc_bf16_conv2d_s2_halo_bwd_data_ok(B, H, W, Cx, cop))
+                     or ((not half) and X3 and lib.dwc_x3_conv2d_s2_bwd_data_ok(B, H, W, Cx, cop)))):
+            # the four output-parity classes of 2x2-tap halo convolutions over dY write every pixel of dx: no ring under the zero rule
+            dx = empty_cl(B, Cx, H, W, dev, dt)
+            if half:
+                w_dg = _prepped(w, "dgrad", cop, Cx, 2, owner, True)
+                _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_s2_halo_bwd_data(
+                    g.data_ptr(), w_dg.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, st), scope_name=ctx.bscope,
+                    detail="dgrad-s2halo" + shape), "conv2d_s2_halo_bwd_data zeropad")
+            elif h2_fits(g):
+                w_h2 = _prepped(w, "h2_dgrad", cop, Cx, 1, owner)
+                ga = amax_of(g)
+                _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_s2_bwd_data(
+                    g.data_ptr(), ga[0], ga[1], w_h2.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, Cx, st), scope_name=ctx.bscope,
+                    exec_flops=3 * flops, detail="dgrad-h2s2" + shape), "h2_conv2d_s2_bwd_data zeropad")
+            else:
+                w_x3 = _prepped(w, "x3_dgrad", cop, Cx, 1, owner)
+                _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_s2_bwd_data(
+                    g.data_ptr(), w_x3.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, Cx, st), scope_name=ctx.bscope,
+                    exec_flops=6 * flops, detail="dgrad-x3s2" + shape), "x3_conv2d_s2_bwd_data zeropad")
+            return dx, False
+        return None, False
 
 
-def conv2d(x, w, b, stride, pad, act="none", bias_grad=True, owner=None, token=None):
-    """Reflect-padded convolution + bias + activation.  Returns Cout channels (a channel
+_PAD_MODES = ("reflect", "zero")
+
+
+def _pad_mode_zero(pad_mode):
+    if pad_mode not in _PAD_MODES:
+        raise ValueError("pad_mode %r: the HIP convolutions take %s" % (pad_mode, " / ".join(_PAD_MODES)))
+    return pad_mode == "zero"
+
+
+def conv2d(x, w, b, stride, pad, act="none", bias_grad=True, owner=None, token=None, pad_mode="reflect"):
+    """Reflect-padded (``pad_mode='zero'``: zero-padded) convolution + bias + activation.  Returns Cout channels (a channel
     slice of the 4-aligned buffer when Cout is not a multiple of 4).  ``bias_grad=False``: the caller feeds the
     result to an instance norm, whose mean subtraction makes the bias gradient identically zero -- it is returned
     as zeros instead of being reduced from dY."""
+    zero = _pad_mode_zero(pad_mode)
     if not bias_grad and ZERO_GRAD_BY_FLAG and isinstance(b, torch.nn.Parameter):
         b._dwc_zero_grad = True            # (see _Conv2d.backward: no gradient tensor for it; FusedAdam / the DP reducer know the flag)
-    y = _Conv2d.apply(x, w, b, int(stride), int(pad), ACT[act], bool(bias_grad), owner, token, not torch.is_grad_enabled())
+    y = _Conv2d.apply(x, w, b, int(stride), int(pad), ACT[act], bool(bias_grad), owner, token, not torch.is_grad_enabled(), zero)
     return y if y.shape[1] == w.shape[0] else y[:, :w.shape[0]]
 
 
-def conv2d_padded(x, w, b, stride, pad, act="none"):
+def conv2d_padded(x, w, b, stride, pad, act="none", pad_mode="reflect"):
     """As conv2d, but returns the 4-aligned channel buffer itself."""
-    return _Conv2d.apply(x, w, b, int(stride), int(pad), ACT[act], True, None)
+    return _Conv2d.apply(x, w, b, int(stride), int(pad), ACT[act], True, None, None, False, _pad_mode_zero(pad_mode))
 
 
 class _HeadsConvWide(torch.autograd.Function):
@@ -1328,13 +1427,15 @@ class _HeadsConvWide(torch.autograd.Function):
         return dx, dw, (db if ctx.needs_input_grad[2] else None), None
 
 
-def conv2d_heads(x, w4, b4, owner=None):
+def conv2d_heads(x, w4, b4, owner=None, pad_mode="reflect"):
     """tanh/sigmoid image heads: [B,C,H,W] features, [P,C,7,7] weights (P = 4 fp32, 8 bf16 with planes 4..7 zero) ->
-    NHWC-P image [B,P,H,W]."""
+    NHWC-P image [B,P,H,W].  ``pad_mode='zero'``: the plain convolution route (the wide filter bank is built for the reflect rule)."""
+    zero = _pad_mode_zero(pad_mode)
     px = 32 // w4.shape[0]
-    if x.shape[3] % px == 0 and w4.shape[2] == w4.shape[3] == 7:
+    if not zero and x.shape[3] % px == 0 and w4.shape[2] == w4.shape[3] == 7:
         return _HeadsConvWide.apply(x, w4, b4, owner)
-    return _Conv2d.apply(x, w4, b4, 1, w4.shape[2] // 2, ACT["heads8" if w4.shape[0] == 8 else "heads"], True, owner)
+    return _Conv2d.apply(x, w4, b4, 1, w4.shape[2] // 2, ACT["heads8" if w4.shape[0] == 8 else "heads"], True, owner, None,
+                         not torch.is_grad_enabled(), zero)
 
 
 class _Conv2dZeroPad(torch.autograd.Function):

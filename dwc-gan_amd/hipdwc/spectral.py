@@ -173,13 +173,15 @@ class _SNEpilogue(torch.autograd.Function):
         return dz, (db[:cout] if db is not None else None), dw, None, None, None, None, None
 
 
-def sn_conv2d(x, module, run, stride, pad, act="none", token=None):
-    """The reference's SpectralNorm(nn.Conv2d) call on the HIP kernels: reflect-padded convolution on ``module.weight_bar``, then the
+def sn_conv2d(x, module, run, stride, pad, act="none", token=None, pad_mode="reflect"):
+    """The reference's SpectralNorm(nn.Conv2d) call on the HIP kernels: reflect-padded (``pad_mode='zero'``: zero-padded, as
+    ops.conv2d) convolution on ``module.weight_bar``, then the
     segmented epilogue with ``run``'s 1 / sigma_s (``run.S`` equal batch segments) + bias + activation.  Returns Cout channels (a
     channel slice of the padded buffer when Cout is not a multiple of 4 / 8)."""
     w_bar = module.weight_bar
     _, _, r = run.layer(module)
-    z = ops._Conv2d.apply(x, w_bar, None, int(stride), int(pad), 0, True, None, token, not torch.is_grad_enabled())
+    z = ops._Conv2d.apply(x, w_bar, None, int(stride), int(pad), 0, True, None, token, not torch.is_grad_enabled(),
+                          ops._pad_mode_zero(pad_mode))
     y = _SNEpilogue.apply(z, module.bias, w_bar, module.weight_u, module.weight_v, r, run.S, ops.ACT[act])
     return y if y.shape[1] == w_bar.shape[0] else y[:, :w_bar.shape[0]]
 

@@ -122,12 +122,14 @@ class SpectralNorm(nn.Module):
 class Conv2dBlock(nn.Module):
     """pad -> conv -> norm -> activation (reference networks.py:524-585) as at most two fused passes.
 
-    What the shipped configurations use -- reflect padding, norm in {none, in, ln, adain}, activation in {relu, lrelu, tanh, sigmoid,
-    none} -- is all HIP: the padding rule inside the convolution's gather, bias / activation in its epilogue, ReLU / LeakyReLU(0.1)
+    What the shipped configurations use or document -- reflect or zero padding at strides 1 and 2, norm in {none, in, ln, adain},
+    activation in {relu, lrelu, tanh, sigmoid, none} -- is all HIP: the padding rule inside the convolution's gather
+    (``pad_type='zero'``: ``ops.conv2d(..., pad_mode='zero')``; hipdwc.ops.ZERO_PAD_HIP = 0 puts ``F.pad`` in front of the unpadded
+    convolution again, stride 1 only), bias / activation in its epilogue, ReLU / LeakyReLU(0.1)
     and the residual add in the norm's apply pass (``dis.norm: in / ln`` with the default ``dis.activ: lrelu``, ``gen.activ: lrelu``;
     hipdwc.ops.NORM_ACT_FUSED = 0 puts lrelu back behind the unfused norm).  The rest of the reference's signature is reachable too
-    (r05), through stock PyTorch-ROCm DEVICE ops around the HIP convolution: ``pad_type`` zero / replicate at stride 1 (``F.pad``, then
-    the convolution without padding), ``activation`` prelu / selu (``nn.PReLU`` / ``F.selu``), and an in / ln / adain norm followed by
+    (r05), through stock PyTorch-ROCm DEVICE ops around the HIP convolution: ``pad_type`` replicate at stride 1 (``F.pad``, then
+    the convolution without padding; stride 2 raises), ``activation`` prelu / selu (``nn.PReLU`` / ``F.selu``), and an in / ln / adain norm followed by
     an activation other than ReLU / LeakyReLU (tanh / sigmoid / prelu / selu: the norm unfused, then the activation).  ``norm='bn'``
     is SegmentedBatchNorm2d on the HIP kernels with none / relu / lrelu
     fused (``segments`` / ``stat_order``: the batch is S equal segments, each with its own batch statistics, the running buffers
@@ -140,9 +142,10 @@ class Conv2dBlock(nn.Module):
         super().__init__()
         if pad_type not in ("reflect", "replicate", "zero"):
             raise AssertionError("Unsupported padding type: {}".format(pad_type))
-        if pad_type != "reflect" and padding > 0 and stride != 1:
-            raise NotImplementedError("pad_type=%r with stride %d: the strided data gradient of the HIP kernels is built for the reflect rule "
-                                      "(4x4, stride 2, pad 1); zero / replicate padding is reachable at stride 1" % (pad_type, stride))
+        if padding > 0 and stride != 1 and (pad_type == "replicate" or (pad_type == "zero" and not ops.ZERO_PAD_HIP)):
+            raise NotImplementedError("pad_type=%r with stride %d: the strided HIP convolutions take the reflect and the zero rule inside "
+                                      "their gather (zero: hipdwc.ops.ZERO_PAD_HIP = 1); a device pad in front of the unpadded "
+                                      "convolution is reachable at stride 1" % (pad_type, stride))
         if activation not in _CONV_ACTS and activation not in ("prelu", "selu"):
             raise AssertionError("Unsupported activation: {}".format(activation))
         self.use_bias = True
@@ -186,19 +189,25 @@ class Conv2dBlock(nn.Module):
         if x.shape[1] < 4:
             x = ops.pack_image(x)
         pad = self.padding
-        if self.pad_type != "reflect" and pad > 0:        # zero / replicate: a device pad in front of the unpadded HIP convolution
+        mode = "zero" if self.pad_type == "zero" and ops.ZERO_PAD_HIP else "reflect"     # the rule inside the convolution's gather
+        if self.pad_type != "reflect" and mode != "zero" and pad > 0:
+            # replicate (and zero with ZERO_PAD_HIP = 0, the A/B partner): a device pad in front of the unpadded HIP convolution
+            if self.stride != 1:
+                raise NotImplementedError("pad_type=%r with stride %d needs hipdwc.ops.ZERO_PAD_HIP = 1" % (self.pad_type, self.stride))
             x = torch.nn.functional.pad(x, (pad,) * 4, mode="constant" if self.pad_type == "zero" else "replicate")
             pad = 0
         fused_act = self.act_kind in _CONV_ACTS
         if self.norm_kind == "sn":
             if sn is None:
                 sn = spectral.sn_power_iteration([self.conv.module], segments or 1)
-            y = spectral.sn_conv2d(x, self.conv.module, sn, self.stride, pad, self.act_kind if fused_act else "none", token=conv_token)
+            y = spectral.sn_conv2d(x, self.conv.module, sn, self.stride, pad, self.act_kind if fused_act else "none", token=conv_token,
+                                   pad_mode=mode)
             if not fused_act:
                 y = self._torch_act(y)
             return y if residual is None else y + residual
         if self.norm is None:
-            y = ops.conv2d(x, self.conv.weight, self.conv.bias, self.stride, pad, self.act_kind if fused_act else "none", token=conv_token)
+            y = ops.conv2d(x, self.conv.weight, self.conv.bias, self.stride, pad, self.act_kind if fused_act else "none", token=conv_token,
+                           pad_mode=mode)
             if not fused_act:
                 y = self._torch_act(y)
             return y if residual is None else y + residual
@@ -209,7 +218,7 @@ class Conv2dBlock(nn.Module):
             train = self.norm.training or not self.norm.track_running_stats
             if not train and getattr(bias, "_dwc_zero_grad", False):
                 bias._dwc_zero_grad = False
-            y = ops.conv2d(x, self.conv.weight, bias, self.stride, pad, "none", bias_grad=not train, token=conv_token)
+            y = ops.conv2d(x, self.conv.weight, bias, self.stride, pad, "none", bias_grad=not train, token=conv_token, pad_mode=mode)
             fused = self.act_kind in batchnorm.ACTS
             y = self.norm(y, act=self.act_kind if fused else "none", segments=segments, stat_order=stat_order)
             if not fused:
@@ -217,12 +226,13 @@ class Conv2dBlock(nn.Module):
             return y if residual is None else y + residual
         if self.act_kind not in (_NORM_ACTS if ops.NORM_ACT_FUSED else ("relu", "none")):
             # prelu / selu / tanh / sigmoid (and lrelu with DWC_NORM_ACT_FUSED=0): the norm on its own, then the activation
-            y = ops.conv2d(x, self.conv.weight, self.conv.bias, self.stride, pad, "none", token=conv_token)
+            y = ops.conv2d(x, self.conv.weight, self.conv.bias, self.stride, pad, "none", token=conv_token, pad_mode=mode)
             y = self.norm(y) if self.norm_kind == "ln" else self.norm(y, relu=False)
             y = torch.relu(y) if self.act_kind == "relu" else (y if self.act_kind == "none" else self._torch_act(y))
             return y if residual is None else y + residual
         y = ops.conv2d(x, self.conv.weight, self.conv.bias, self.stride, pad, "none",
-                       bias_grad=self.norm_kind == "ln", token=conv_token)   # IN / AdaIN subtract the per-(n,c) mean: d/d bias == 0
+                       bias_grad=self.norm_kind == "ln", token=conv_token,   # IN / AdaIN subtract the per-(n,c) mean: d/d bias == 0
+                       pad_mode=mode)
         if self.norm_kind == "ln":
             y = self.norm(y, act=self.act_kind)
             return y if residual is None else y + residual
@@ -256,9 +266,10 @@ class ResBlock(nn.Module):
         inside its batch)."""
         c0, c1 = self.model[0], self.model[1]
         acts = ("relu", "lrelu") if ops.NORM_ACT_FUSED else ("relu",)
-        if c0.norm_kind != "adain" or c0.act_kind not in acts or c0.pad_type != "reflect" or c1.norm_kind != "adain":
+        in_kernel = c0.pad_type == "reflect" or (c0.pad_type == "zero" and ops.ZERO_PAD_HIP)
+        if c0.norm_kind != "adain" or c0.act_kind not in acts or not in_kernel or c1.norm_kind != "adain":
             return self.forward(torch.cat([x] * groups), 1)
-        y = ops.conv2d(x, c0.conv.weight, c0.conv.bias, c0.stride, c0.padding, "none", bias_grad=False)
+        y = ops.conv2d(x, c0.conv.weight, c0.conv.bias, c0.stride, c0.padding, "none", bias_grad=False, pad_mode=c0.pad_type)
         h = c0.norm(torch.cat([y] * groups), act=c0.act_kind)
         return c1(h, residual=torch.cat([x] * groups))
 
@@ -387,7 +398,15 @@ class Decoder(nn.Module):
             if extra:
                 ws.append(wa.new_zeros((extra,) + tuple(wa.shape[1:])))
                 bs.append(ba.new_zeros(extra))
-            return ops.conv2d_heads(feat, torch.cat(ws, 0), torch.cat(bs, 0), owner=owner)
+            return ops.conv2d_heads(feat, torch.cat(ws, 0), torch.cat(bs, 0), owner=owner, pad_mode=self._heads_pad_mode())
+
+    def _heads_pad_mode(self):
+        """The padding rule of the two fused image heads (they are built with the same pad_type)."""
+        kind = self.image_content.pad_type
+        if kind != self.image_attention.pad_type or kind == "replicate" or (kind == "zero" and not ops.ZERO_PAD_HIP):
+            raise NotImplementedError("fused image heads: pad_type %r / %r is not on the HIP path (reflect, or zero with "
+                                      "hipdwc.ops.ZERO_PAD_HIP = 1)" % (kind, self.image_attention.pad_type))
+        return kind
 
     def forward(self, x):
         heads = self.forward_nhwc4(x)

@@ -230,6 +230,19 @@ size_t dwc_conv2d_bwd_data_zeropad_ws_bytes(int B, int H, int W, int Cin, int Co
 int dwc_conv2d_bwd_data_zeropad(const float* dy, const float* w_dgrad, float* dx,
                                 int B, int H, int W, int Cin, int Cout, int KH, int KW, int pad,
                                 void* ws, size_t ws_bytes, void* stream);
+/* Zero-padded convolutions WITH trainable weights (Conv2dBlock pad_type 'zero', reference networks.py:561-562), additive in ABI 11.
+ * dwc_conv2d_bwd_weight_zeropad: dwc_conv2d_bwd_weight with the zero rule -- a gathered pixel outside the image contributes 0; every
+ * stride and pad that entry takes, the same plan (dwc_conv2d_bwd_weight_plan) and the same scratch.
+ * dwc_conv2d_bwd_data_crop: dx:[B,H,W,Cin] of a zero-padded convolution at stride 1 (any filter) or stride 2 (4x4, pad 1, even H and
+ * W) -- the shapes dwc_conv2d_bwd_data takes.  The adjoint of zero padding is a crop: the interior of the gradient of the padded
+ * image is dx, nothing is folded.  ws = [padded gradient image][split-K partials], sized by _ws_bytes (0 for pad 0 and an unsplit
+ * plan; DWC_EWORKSPACE when too small); w_dgrad as for dwc_conv2d_bwd_data. */
+size_t dwc_conv2d_bwd_weight_zeropad_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
+int dwc_conv2d_bwd_weight_zeropad(const float* x, const float* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int KH, int KW,
+                                  int stride, int pad, int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream);
+size_t dwc_conv2d_bwd_data_crop_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
+int dwc_conv2d_bwd_data_crop(const float* dy, const float* w_dgrad, float* dx, int B, int H, int W, int Cin, int Cout, int KH, int KW,
+                             int stride, int pad, void* ws, size_t ws_bytes, void* stream);
 /* F.max_pool2d(x, 2, 2) on NHWC (reference networks.py:666,671,677); ties to the first element in scan order. */
 int dwc_maxpool2_fwd(const float* x, float* y, int B, int H, int W, int C, void* stream);
 int dwc_maxpool2_bwd(const float* x, const float* dy, float* dx, int B, int H, int W, int C, void* stream);
@@ -556,6 +569,35 @@ int dwc_bf16_conv2d_fwd_zeropad(const void* x, const void* w_prepared, const flo
 size_t dwc_bf16_conv2d_bwd_data_zeropad_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int pad);
 int dwc_bf16_conv2d_bwd_data_zeropad(const void* dy, const void* w_dgrad, void* dx, int B, int H, int W, int Cin, int Cout, int KH,
                                      int KW, int pad, void* ws, size_t ws_bytes, void* stream);
+/* The halo weight-gradient kernels under the zero rule (additive in ABI 11): dwc_x3_conv2d_wgrad / dwc_h2_conv2d_wgrad /
+ * dwc_bf16_conv2d_wgrad_halo for the ZERO-padded convolution (pad (K-1)/2 at stride 1, K = 3, 5; pad 1 for the 4x4 stride-2 layer).
+ * Same shapes (the *_wgrad_ws_bytes / _wgrad_halo_ws_bytes queries answer for them), plan and scratch; x of less than 2 GiB. */
+int dwc_x3_conv2d_wgrad_zeropad(const float* x, const float* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int K,
+                                int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream);
+int dwc_h2_conv2d_wgrad_zeropad(const float* x, const void* x_amax, unsigned x_epoch, const float* dy, const void* dy_amax,
+                                unsigned dy_epoch, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int K, int cin_real,
+                                int cout_real, void* ws, size_t ws_bytes, void* stream);
+int dwc_bf16_conv2d_wgrad_halo_zeropad(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int K,
+                                       int cin_real, int cout_real, void* ws, size_t ws_bytes, void* stream);
+/* The stride-2 halo forwards under the zero rule (additive in ABI 11): dwc_x3_conv2d_s2_ws / dwc_h2_conv2d_s2_ws /
+ * dwc_bf16_conv2d_s2_halo for the ZERO-padded 4x4 stride-2 pad-1 convolution; shapes (dwc_x3_conv2d_s2_ok /
+ * dwc_bf16_conv2d_s2_halo_ok), prepared weights and scratch of the reflect twins. */
+int dwc_x3_conv2d_s2_ws_zeropad(const float* x, const void* w_prepared, const float* bias, float* y, int B, int H, int W, int Cin, int N,
+                                int rows, int act, void* ws, size_t ws_bytes, unsigned* tickets, void* stream);
+int dwc_h2_conv2d_s2_ws_zeropad(const float* x, const void* x_amax, unsigned x_epoch, const void* w_prepared, const float* bias, float* y,
+                                void* y_amax, unsigned y_epoch, int B, int H, int W, int Cin, int N, int rows, int act, void* ws,
+                                size_t ws_bytes, unsigned* tickets, void* stream);
+int dwc_bf16_conv2d_s2_halo_zeropad(const void* x, const void* w_prepared, const float* bias, void* y, int B, int H, int W, int Cin,
+                                    int Cout, int act, void* stream);
+/* bf16 forms of dwc_conv2d_bwd_weight_zeropad / dwc_conv2d_bwd_data_crop (tensors of at most 2 GiB: the zero rule is an offset past
+ * the buffer descriptor) */
+size_t dwc_bf16_conv2d_bwd_weight_zeropad_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
+int dwc_bf16_conv2d_bwd_weight_zeropad(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int KH,
+                                       int KW, int stride, int pad, int cin_real, int cout_real, void* ws, size_t ws_bytes,
+                                       void* stream);
+size_t dwc_bf16_conv2d_bwd_data_crop_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
+int dwc_bf16_conv2d_bwd_data_crop(const void* dy, const void* w_dgrad, void* dx, int B, int H, int W, int Cin, int Cout, int KH, int KW,
+                                  int stride, int pad, void* ws, size_t ws_bytes, void* stream);
 int dwc_bf16_maxpool2_fwd(const void* x, void* y, int B, int H, int W, int C, void* stream);
 int dwc_bf16_maxpool2_bwd(const void* x, const void* dy, void* dx, int B, int H, int W, int C, void* stream);
 
