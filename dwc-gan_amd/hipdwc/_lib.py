@@ -25,6 +25,13 @@ class AdvSpec(ctypes.Structure):               # struct dwc_adv_spec (passed by 
 BN_MAX_SEGMENTS = 8                            # DWC_BN_MAX_SEGMENTS
 
 
+TXT_MAX_LAYERS = 4                            # DWC_TXT_MAX_LAYERS
+
+
+class TxtLayers(ctypes.Structure):             # struct dwc_txt_layers (passed by value)
+    _fields_ = [("n", c_int), ("out", c_fp * TXT_MAX_LAYERS), ("c", c_fp * TXT_MAX_LAYERS)]
+
+
 class BnOrder(ctypes.Structure):               # struct dwc_bn_order (passed by value)
     _fields_ = [("n", c_int), ("idx", c_int * BN_MAX_SEGMENTS)]
 
@@ -241,6 +248,14 @@ SIGNATURES = {
     "dwc_x3_conv2d_s2_ws_zeropad": (c_int, [c_fp] * 4 + [c_int] * 7 + [c_fp, c_sz, c_fp, c_fp]),
     "dwc_h2_conv2d_s2_ws_zeropad": (c_int, [c_fp, c_fp, c_u, c_fp, c_fp, c_fp, c_fp, c_u] + [c_int] * 7 + [c_fp, c_sz, c_fp, c_fp]),
     "dwc_bf16_conv2d_s2_halo_zeropad": (c_int, [c_fp, c_fp, c_fp, c_fp] + [c_int] * 6 + [c_fp]),
+    # ---- text encoder: operand, inter-layer and final-state movement (hipdwc.txt; additive in ABI 11) ----
+    "dwc_txt_operand_fwd": (c_int, [c_fp] * 6 + [c_int] * 6 + [c_fp]),
+    "dwc_txt_operand_bwd": (c_int, [c_fp] * 8 + [c_int] * 5 + [c_fp]),
+    "dwc_txt_prev_state": (c_int, [c_fp, c_fp] + [c_int] * 3 + [c_fp]),
+    "dwc_txt_inter_fwd": (c_int, [c_fp] * 4 + [c_int] * 3 + [c_fp]),
+    "dwc_txt_inter_bwd": (c_int, [c_fp] * 7 + [c_int, c_fp] + [c_int] * 3 + [c_fp]),
+    "dwc_txt_states_fwd": (c_int, [TxtLayers, c_fp, c_fp, c_fp] + [c_int] * 3 + [c_fp]),
+    "dwc_txt_states_bwd": (c_int, [c_fp, c_fp, c_fp, TxtLayers] + [c_int] * 3 + [c_fp]),
 }
 
 ABI_VERSION = 11             # DWC_ABI_VERSION of include/dwcgan_hip.h

@@ -1714,21 +1714,26 @@ def _gemm_nn(dy, w, owner):
     return dx
 
 
-def _gemm_tn(dy, x, out=None):
+def _gemm_tn(dy, x, out=None, raw=None):
     """dy:[M,N]^T @ x:[M,K] -> [N,K] (the weight gradient of `_gemm_nt`; into `out` when given): the weight-gradient kernel of the
-    same one-filter layer."""
+    same one-filter layer.  `raw`: a [N, c, taps] buffer (c = _pow2_div(K)) that receives the kernel's own layout and is returned as it
+    is -- a caller with several products re-lays them out in one copy."""
     lib = _lib.load()
     M, N = dy.shape
     K = x.shape[1]
     c = _pow2_div(K)
     taps = K // c
-    dw4 = torch.empty((N, c, 1, taps), dtype=torch.float32, device=x.device)
+    if raw is not None:
+        assert raw.shape == (N, c, taps) and raw.is_contiguous() and raw.dtype == torch.float32
+    dw4 = torch.empty((N, c, 1, taps), dtype=torch.float32, device=x.device) if raw is None else raw
     nws = lib.dwc_conv2d_bwd_weight_ws_bytes(M, 1, taps, c, N, 1, taps, 1, 0)
     ws = workspace(nws, x.device)
     flops = 2.0 * M * N * K
     _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: lib.dwc_conv2d_bwd_weight(
         x.data_ptr(), dy.data_ptr(), dw4.data_ptr(), M, 1, taps, c, N, 1, taps, 1, 0, c, N, ws.data_ptr(), ws.numel(), _stream()),
         detail="wgrad B%d 1x%d %d>%d k%d s1" % (M, taps, c, N, taps)), "gemm_tn")
+    if raw is not None:
+        return raw
     if out is None:
         return dw4.squeeze(2).permute(0, 2, 1).reshape(N, K)
     out.view(N, taps, c).copy_(dw4.squeeze(2).permute(0, 2, 1))
@@ -1767,6 +1772,7 @@ def linear_any(x, w, b, owner=None):
 # --------------------------------------------------------------------------------------
 # text encoder: one bidirectional LSTM layer over padded sequences with per-sample lengths
 # --------------------------------------------------------------------------------------
+TXT_FUSED = int(os.environ.get("DWC_TXT_FUSED", "1"))     # 0: the text encoder's data movement as stock tensor ops (hipdwc.txt)
 LSTM_GEMM = int(os.environ.get("DWC_LSTM_GEMM", "1"))     # 0: the layer's dense products through torch (rocBLAS / hipBLASLt)
 _LSTM_STATUS = {}            # device index -> (persistent int32 device word, pinned host copy, event of the last copy or None)
 LSTM_SEQ_MAX_WORKGROUPS = 0  # > 0: cap on the persistent launches' grid (hipdwc.dp sets it while collectives share the CUs)
@@ -1805,113 +1811,167 @@ def lstm_status_poll(device, wait=False):
         ent[2].record()
 
 
+_LSTM_DERIVED = {}     # (kind, id(first owner parameter)) -> (weakref, stamp, tensor derived from the owners' values)
+
+
+def _stamp(params):
+    """Validity stamp of values derived from `params`, as `_prepped` keys its layouts: (version counter, storage address) of each."""
+    return None if params is None else tuple((p._version, p.data_ptr()) for p in params)
+
+
+def _lstm_derived(kind, owners, stamp, build):
+    """`build()` -- a tensor computed from stacked LSTM parameters alone -- kept until one of `owners` (the direction parameters the
+    stack was made from) changes.  `stamp`: their `_stamp` at the time the stacked values were read, so a backward that runs after
+    an optimiser step neither finds nor leaves an entry that does not belong to its values.  Without owners: built on every call."""
+    if owners is None:
+        return build()
+    key = (kind, id(owners[0]))
+    ent = _LSTM_DERIVED.get(key)
+    if ent is not None and ent[0]() is owners[0] and ent[1] == stamp:
+        return ent[2]
+    buf = build()
+    _LSTM_DERIVED[key] = (weakref.ref(owners[0], lambda _r, key=key: _LSTM_DERIVED.pop(key, None)), stamp, buf)
+    return buf
+
+
+def lstm_layer_fwd(x, lens, w_ih, w_hh, b_ih, b_hh, owners=None, owners_hh=None, owners_b=None):
+    """Forward of one bidirectional layer (see `_LSTMBidir`) outside autograd: (out, c, saved) with `saved` what `lstm_layer_bwd`
+    needs.  x:[T,B,I] contiguous."""
+    _require_device(x)
+    lib = _lib.load()
+    T, B, I = x.shape
+    H = w_hh.shape[2]
+    dev = x.device
+    X = x.reshape(T * B, I)
+    # owners: the two direction parameters weight_ih is stacked from (cache key of the prepared layouts; without them the
+    # dense products stay with torch: the stacked tensor is a cached buffer whose address may be reused)
+    hip_gemm = bool(LSTM_GEMM and owners is not None and gemm_ok(I, 4 * H) and gemm_ok(H, 4 * H))
+    if hip_gemm:
+        bsum = _lstm_derived("bsum", owners_b, _stamp(owners_b), lambda: b_ih.detach() + b_hh.detach())
+        X = X.contiguous()
+        xproj = torch.empty((2, T * B, 4 * H), dtype=torch.float32, device=dev)                               # [2,TB,4H]
+        for d in range(2):
+            _gemm_nt(X, w_ih[d], bsum[d], owners[d], out=xproj[d])
+    else:
+        xproj = torch.baddbmm((b_ih + b_hh).unsqueeze(1), X.unsqueeze(0).expand(2, -1, -1), w_ih.transpose(1, 2))   # [2,TB,4H]
+    w_hh_c = w_hh.contiguous()
+    out = torch.empty((2, T, B, H), dtype=torch.float32, device=dev)
+    c = torch.empty((2, T, B, H), dtype=torch.float32, device=dev)
+    gates = torch.empty((2, T, B, 4 * H), dtype=torch.float32, device=dev)
+    rc = -1
+    if LSTM_SEQ:
+        # all T steps in ONE persistent launch (csrc/lstm.hip lstm_seq_fwd); shapes it does not take fall to the step kernels
+        ws = workspace(lib.dwc_lstm_seq_ws_bytes(B, 2), dev)
+        rc = lib.dwc_lstm_seq_fwd(xproj.data_ptr(), w_hh_c.data_ptr(), lens.data_ptr(), out.data_ptr(), c.data_ptr(),
+                                  gates.data_ptr(), T, B, H, 2, ws.data_ptr(), ws.numel(), _lstm_status(dev)[0].data_ptr(),
+                                  LSTM_SEQ_MAX_WORKGROUPS, _stream())
+        if rc not in (0, _lib.EINVAL):
+            _lib.check(rc, "lstm_seq_fwd")
+    if rc != 0:
+        _lib.check(lib.dwc_lstm_fwd(xproj.data_ptr(), w_hh_c.data_ptr(), lens.data_ptr(), out.data_ptr(), c.data_ptr(),
+                                    gates.data_ptr(), T, B, H, 2, _stream()), "lstm_fwd")
+    saved = {"tensors": (X, lens, w_ih, w_hh_c, out, c, gates), "shape": (T, B, I, H), "hip_gemm": hip_gemm, "owners": owners,
+             "owners_hh": owners_hh, "hh_stamp": _stamp(owners_hh)}
+    return out, c, saved
+
+
+def lstm_layer_bwd(saved, d_out, d_c, need_x=True, need_w_ih=True, need_w_hh=True, need_b=True, split_dx=False):
+    """Backward of `lstm_layer_fwd`: (dx, dw_ih, dw_hh, db), None where not needed.  d_out, d_c: [2,T,B,H] or None.  `split_dx`: dx
+    comes back as the pair (dx_a, dx_b) with dx = dx_a + dx_b (dx_b None when there is one tensor only) for a caller whose next
+    kernel adds the two directions' input gradients while it reads them."""
+    lib = _lib.load()
+    X, lens, w_ih, w_hh, out, c, gates = saved["tensors"]
+    T, B, I, H = saved["shape"]
+    dev = X.device
+    d_out = None if d_out is None else d_out.contiguous()
+    d_c = None if d_c is None else d_c.contiguous()
+    w_hh_t = _lstm_derived("w_hh_t", saved["owners_hh"], saved["hh_stamp"], lambda: w_hh.transpose(1, 2).contiguous())
+    dgates = torch.empty((2, T, B, 4 * H), dtype=torch.float32, device=dev)
+    carry = torch.empty((2, B, H), dtype=torch.float32, device=dev)
+    rc = -1
+    if LSTM_SEQ:
+        ws = workspace(lib.dwc_lstm_seq_ws_bytes(B, 2), dev)
+        rc = lib.dwc_lstm_seq_bwd(_p(d_out), _p(d_c), w_hh_t.data_ptr(), lens.data_ptr(), c.data_ptr(), gates.data_ptr(),
+                                  dgates.data_ptr(), T, B, H, 2, ws.data_ptr(), ws.numel(), _lstm_status(dev)[0].data_ptr(),
+                                  LSTM_SEQ_MAX_WORKGROUPS, _stream())
+        if rc not in (0, _lib.EINVAL):
+            _lib.check(rc, "lstm_seq_bwd")
+    if rc != 0:
+        _lib.check(lib.dwc_lstm_bwd(_p(d_out), _p(d_c), w_hh_t.data_ptr(), lens.data_ptr(), c.data_ptr(), gates.data_ptr(),
+                                    dgates.data_ptr(), carry.data_ptr(), T, B, H, 2, _stream()), "lstm_bwd")
+    dG = dgates.view(2, T * B, 4 * H)
+    dGt = dG.transpose(1, 2)
+    hip = saved["hip_gemm"]
+
+    def relaid(raw, K):
+        # the weight-gradient kernel writes [4H, c, taps]; the parameter is [4H, taps * c]: ONE copy for both directions
+        return raw.transpose(2, 3).reshape(2, 4 * H, K)
+
+    dw_ih = None
+    if need_w_ih:                                                                               # [2,4H,I]
+        if hip:
+            raw = torch.empty((2, 4 * H, _pow2_div(I), I // _pow2_div(I)), dtype=torch.float32, device=dev)
+            for d in range(2):
+                _gemm_tn(dG[d], X, raw=raw[d])
+            dw_ih = relaid(raw, I)
+        else:
+            dw_ih = torch.matmul(dGt, X)
+    db = dG.sum(1) if need_b else None
+    dw_hh = None
+    if need_w_hh:
+        # state entering step t: the previous slot in processing order (zeros at the ends and past each length), built in one
+        # launch.  (Contracting row ranges of dgates and out instead -- no copy at all -- changes the rows per split of the
+        # weight-gradient kernel and with them the last bits of dw_hh; a run would no longer reproduce its predecessor's.)
+        hprev = torch.empty((2, T, B, H), dtype=torch.float32, device=dev)
+        _lib.check(lib.dwc_txt_prev_state(out.data_ptr(), hprev.data_ptr(), T, B, H, _stream()), "txt_prev_state")
+        hp = hprev.view(2, T * B, H)
+        if hip:
+            raw = torch.empty((2, 4 * H, _pow2_div(H), H // _pow2_div(H)), dtype=torch.float32, device=dev)
+            for d in range(2):
+                _gemm_tn(dG[d], hp[d], raw=raw[d])
+            dw_hh = relaid(raw, H)
+        else:
+            dw_hh = torch.bmm(dGt, hp)                                                                     # [2,4H,H]
+    dx = None
+    if need_x:
+        if hip:
+            parts = (_gemm_nn(dG[0], w_ih[0], saved["owners"][0]).view(T, B, I), _gemm_nn(dG[1], w_ih[1], saved["owners"][1]).view(T, B, I))
+            dx = parts if split_dx else parts[0] + parts[1]
+        else:
+            dx = torch.bmm(dG, w_ih).sum(0).view(T, B, I)
+            dx = (dx, None) if split_dx else dx
+    return dx, dw_ih, dw_hh, db
+
+
 class _LSTMBidir(torch.autograd.Function):
     """Both directions of one nn.LSTM layer on a packed batch (reference networks_v2.py:226-233), zero initial state.
     x:[T,B,I]; lens:[B] int32 on the device (sample b is active at steps t < lens[b]); w_ih:[2,4H,I], w_hh:[2,4H,H],
     b_ih, b_hh:[2,4H] (direction 0 forward, 1 reverse).  Returns out (h_t) and c, both [2,T,B,H] with zeros at the
     inactive slots.  The input projection and the four weight/input gradient products are library GEMMs; the T sequential
-    steps run in dwc_lstm_fwd / dwc_lstm_bwd."""
+    steps run in dwc_lstm_fwd / dwc_lstm_bwd.  (The work itself is `lstm_layer_fwd` / `lstm_layer_bwd`, which hipdwc.txt calls
+    directly.)"""
 
     @staticmethod
-    def forward(ctx, x, lens, w_ih, w_hh, b_ih, b_hh, owners=None):
-        _require_device(x)
-        lib = _lib.load()
-        T, B, I = x.shape
-        H = w_hh.shape[2]
-        dev = x.device
-        X = x.reshape(T * B, I)
-        # owners: the two direction parameters weight_ih is stacked from (cache key of the prepared layouts; without them the
-        # dense products stay with torch: the stacked tensor is a cached buffer whose address may be reused)
-        ctx.hip_gemm = bool(LSTM_GEMM and owners is not None and gemm_ok(I, 4 * H) and gemm_ok(H, 4 * H))
-        ctx.owners = owners
-        if ctx.hip_gemm:
-            bsum = b_ih + b_hh
-            X = X.contiguous()
-            xproj = torch.empty((2, T * B, 4 * H), dtype=torch.float32, device=dev)                               # [2,TB,4H]
-            for d in range(2):
-                _gemm_nt(X, w_ih[d], bsum[d], owners[d], out=xproj[d])
-        else:
-            xproj = torch.baddbmm((b_ih + b_hh).unsqueeze(1), X.unsqueeze(0).expand(2, -1, -1), w_ih.transpose(1, 2))   # [2,TB,4H]
-        w_hh_c = w_hh.contiguous()
-        out = torch.empty((2, T, B, H), dtype=torch.float32, device=dev)
-        c = torch.empty((2, T, B, H), dtype=torch.float32, device=dev)
-        gates = torch.empty((2, T, B, 4 * H), dtype=torch.float32, device=dev)
-        rc = -1
-        if LSTM_SEQ:
-            # all T steps in ONE persistent launch (csrc/lstm.hip lstm_seq_fwd); shapes it does not take fall to the step kernels
-            ws = workspace(lib.dwc_lstm_seq_ws_bytes(B, 2), dev)
-            rc = lib.dwc_lstm_seq_fwd(xproj.data_ptr(), w_hh_c.data_ptr(), lens.data_ptr(), out.data_ptr(), c.data_ptr(),
-                                      gates.data_ptr(), T, B, H, 2, ws.data_ptr(), ws.numel(), _lstm_status(dev)[0].data_ptr(),
-                                      LSTM_SEQ_MAX_WORKGROUPS, _stream())
-            if rc not in (0, _lib.EINVAL):
-                _lib.check(rc, "lstm_seq_fwd")
-        if rc != 0:
-            _lib.check(lib.dwc_lstm_fwd(xproj.data_ptr(), w_hh_c.data_ptr(), lens.data_ptr(), out.data_ptr(), c.data_ptr(),
-                                        gates.data_ptr(), T, B, H, 2, _stream()), "lstm_fwd")
-        ctx.save_for_backward(X, lens, w_ih, w_hh_c, out, c, gates)
-        ctx.shape = (T, B, I, H)
+    def forward(ctx, x, lens, w_ih, w_hh, b_ih, b_hh, owners=None, owners_hh=None, owners_b=None):
+        out, c, saved = lstm_layer_fwd(x, lens, w_ih, w_hh, b_ih, b_hh, owners, owners_hh, owners_b)
+        ctx.save_for_backward(*saved.pop("tensors"))
+        ctx.saved = saved
         return out, c
 
     @staticmethod
     def backward(ctx, d_out, d_c):
-        lib = _lib.load()
-        X, lens, w_ih, w_hh, out, c, gates = ctx.saved_tensors
-        T, B, I, H = ctx.shape
-        dev = X.device
-        d_out = None if d_out is None else d_out.contiguous()
-        d_c = None if d_c is None else d_c.contiguous()
-        w_hh_t = w_hh.transpose(1, 2).contiguous()
-        dgates = torch.empty((2, T, B, 4 * H), dtype=torch.float32, device=dev)
-        carry = torch.empty((2, B, H), dtype=torch.float32, device=dev)
-        rc = -1
-        if LSTM_SEQ:
-            ws = workspace(lib.dwc_lstm_seq_ws_bytes(B, 2), dev)
-            rc = lib.dwc_lstm_seq_bwd(_p(d_out), _p(d_c), w_hh_t.data_ptr(), lens.data_ptr(), c.data_ptr(), gates.data_ptr(),
-                                      dgates.data_ptr(), T, B, H, 2, ws.data_ptr(), ws.numel(), _lstm_status(dev)[0].data_ptr(),
-                                      LSTM_SEQ_MAX_WORKGROUPS, _stream())
-            if rc not in (0, _lib.EINVAL):
-                _lib.check(rc, "lstm_seq_bwd")
-        if rc != 0:
-            _lib.check(lib.dwc_lstm_bwd(_p(d_out), _p(d_c), w_hh_t.data_ptr(), lens.data_ptr(), c.data_ptr(), gates.data_ptr(),
-                                        dgates.data_ptr(), carry.data_ptr(), T, B, H, 2, _stream()), "lstm_bwd")
-        dG = dgates.view(2, T * B, 4 * H)
-        dGt = dG.transpose(1, 2)
-        hip = ctx.hip_gemm
-        dw_ih = None
-        if ctx.needs_input_grad[2]:                                                             # [2,4H,I]
-            if hip:
-                dw_ih = torch.empty((2, 4 * H, I), dtype=torch.float32, device=dev)
-                for d in range(2):
-                    _gemm_tn(dG[d], X, out=dw_ih[d])
-            else:
-                dw_ih = torch.matmul(dGt, X)
-        db = dG.sum(1) if (ctx.needs_input_grad[4] or ctx.needs_input_grad[5]) else None
-        dw_hh = None
-        if ctx.needs_input_grad[3]:
-            # state entering step t: the previous slot in processing order (zeros at the ends and past each length)
-            hprev = torch.zeros((2, T, B, H), dtype=torch.float32, device=dev)
-            hprev[0, 1:] = out[0, :-1]
-            hprev[1, :-1] = out[1, 1:]
-            hp = hprev.view(2, T * B, H)
-            if hip:
-                dw_hh = torch.empty((2, 4 * H, H), dtype=torch.float32, device=dev)
-                for d in range(2):
-                    _gemm_tn(dG[d], hp[d], out=dw_hh[d])
-            else:
-                dw_hh = torch.bmm(dGt, hp)                                                                     # [2,4H,H]
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if hip:
-                dx = (_gemm_nn(dG[0], w_ih[0], ctx.owners[0]) + _gemm_nn(dG[1], w_ih[1], ctx.owners[1])).view(T, B, I)
-            else:
-                dx = torch.bmm(dG, w_ih).sum(0).view(T, B, I)
-        return dx, None, dw_ih, dw_hh, db, db, None
+        saved = dict(ctx.saved, tensors=ctx.saved_tensors)
+        need = ctx.needs_input_grad
+        dx, dw_ih, dw_hh, db = lstm_layer_bwd(saved, d_out, d_c, need[0], need[2], need[3], need[4] or need[5])
+        return dx, None, dw_ih, dw_hh, db, db, None, None, None
 
 
-def lstm_bidir(x, lens, w_ih, w_hh, b_ih, b_hh, owners=None):
+def lstm_bidir(x, lens, w_ih, w_hh, b_ih, b_hh, owners=None, owners_hh=None, owners_b=None):
     """``owners``: (weight_ih of direction 0, of direction 1) -- the parameters ``w_ih`` was stacked from; given, the layer's
-    dense products (input projection, its input and weight gradients, the recurrent weight gradient) run on the HIP GEMM kernels."""
-    return _LSTMBidir.apply(x.contiguous(), lens, w_ih, w_hh, b_ih, b_hh, owners)
+    dense products (input projection, its input and weight gradients, the recurrent weight gradient) run on the HIP GEMM kernels.
+    ``owners_hh``: the same for ``w_hh``; given, the transposed copy the backward recurrence reads is kept until they change.
+    ``owners_b``: the four bias parameters (b_ih then b_hh); given, their sum is kept likewise."""
+    return _LSTMBidir.apply(x.contiguous(), lens, w_ih, w_hh, b_ih, b_hh, owners, owners_hh, owners_b)
 
 
 # --------------------------------------------------------------------------------------

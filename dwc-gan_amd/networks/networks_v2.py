@@ -3,15 +3,16 @@
 ``AdaINGen_v2`` keeps the constructor, ``encode`` / ``encode_txt`` / ``decode`` methods, attribute
 names and ``state_dict`` keys of reference networks/networks_v2.py:9-95; the conv / norm /
 upsample stacks run on libdwcgan_hip.so through ``hipdwc.ops``.  The text encoder's packed
-bi-LSTM runs its sequential part on the HIP recurrent kernels (``ops.lstm_bidir``; embedding lookup
-and the input / weight-gradient GEMMs are library calls), with the reference's batch-mixing
-``view`` reproduced on purpose.
+bi-LSTM runs its sequential part on the HIP recurrent kernels (``ops.lstm_bidir``), its dense
+products on the GEMM kernels and the data movement around them (embedding lookup, operands,
+final states) on the kernels of ``hipdwc.txt``, with the reference's batch-mixing ``view``
+reproduced on purpose.
 """
 import numpy as np
 import torch
 from torch import nn
 
-from hipdwc import host, ops
+from hipdwc import host, ops, txt
 from .networks import ContentEncoder, MLP, Conv2dBlock, ResBlocks, AdaptiveInstanceNorm2d, Decoder  # noqa: F401
 
 
@@ -141,6 +142,12 @@ class TxtEncoder(nn.Module):
             self.fcvars.append(nn.Linear(feat, c_dim))
 
     def forward(self, style_ord, src_tokens, src_lengths):
+        if not self.bidirectional:
+            raise NotImplementedError("the HIP text encoder is bidirectional (the reference's only configuration)")
+        if ops.TXT_FUSED and src_tokens.is_cuda:
+            # everything up to the heads' feature row on the kernels of csrc/txt_glue.hip: one launch per tensor built here
+            return self._heads(txt.encode(self, style_ord, src_tokens, src_lengths, _packed_index))
+        # DWC_TXT_FUSED=0: the same computation as stock tensor ops (the reference of tests/test_txt_fused.py)
         noise = host.noise()
         tokens = src_tokens.transpose(1, 0)
         seq_len, bsz = tokens.shape
@@ -166,15 +173,16 @@ class TxtEncoder(nn.Module):
         t_max = int(lens_list[0])
         data = torch.cat([emb, sty.expand(seq_len, -1, -1)], -1)[:t_max]
         cols = torch.arange(bsz, device=tokens.device)
-        suffixes = ("", "_reverse") if self.bidirectional else ("",)
-        if not self.bidirectional:
-            raise NotImplementedError("the HIP text encoder is bidirectional (the reference's only configuration)")
+        suffixes = ("", "_reverse")
         hs, cs = [], []
         for l in range(self.num_layers):
             par = {n: ops.cat_params([getattr(self.lstm, "%s_l%d%s" % (n, l, suf)) for suf in suffixes], stack=True)
                    for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")}
             out, cell = ops.lstm_bidir(data, lens_dev, par["weight_ih"], par["weight_hh"], par["bias_ih"], par["bias_hh"],
-                                       owners=tuple(getattr(self.lstm, "weight_ih_l%d%s" % (l, suf)) for suf in suffixes))
+                                       owners=tuple(getattr(self.lstm, "weight_ih_l%d%s" % (l, suf)) for suf in suffixes),
+                                       owners_hh=tuple(getattr(self.lstm, "weight_hh_l%d%s" % (l, suf)) for suf in suffixes),
+                                       owners_b=tuple(getattr(self.lstm, "%s_l%d%s" % (n, l, suf)) for n in ("bias_ih", "bias_hh")
+                                                      for suf in suffixes))
             # final states: forward direction at each sample's last token, reverse direction at t = 0
             hs += [out[0][last, cols], out[1][0]]
             cs += [cell[0][last, cols], cell[1][0]]
@@ -197,7 +205,9 @@ class TxtEncoder(nn.Module):
         h_n, c_n = _Permute.apply(h_n, 1, unsort, order), _Permute.apply(c_n, 1, unsort, order)
         # reference networks_v2.py:249: concatenating along the BATCH axis and then viewing as
         # (batch, -1) interleaves samples of the local batch; reproduced, not fixed
-        feat = torch.cat([h_n, c_n], dim=1).view(bsz, -1)
+        return self._heads(torch.cat([h_n, c_n], dim=1).view(bsz, -1))
+
+    def _heads(self, feat):
         # the 2*num_class heads read the same feature row: one [2*num_class*c_dim, feat] product
         w = ops.cat_params([m.weight for m in self.fcs] + [m.weight for m in self.fcvars])
         b = ops.cat_params([m.bias for m in self.fcs] + [m.bias for m in self.fcvars])

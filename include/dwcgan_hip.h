@@ -822,6 +822,51 @@ int dwc_bf16_batchnorm_bwd(const void* dy, const void* x, const float* mean, con
                            const float* beta, void* dx, float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act,
                            int training, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- text encoder: the data movement around its bi-LSTM layers in one launch each (additive in ABI 11; csrc/txt_glue.hip,
+ *      DESIGN.md 18; reference networks_v2.py:199-249) ---------------------------------------------------------------------------------
+ * All tensors fp32 and dense.  j is a sample's position in the length-sorted batch; order[j] its position in the caller's batch,
+ * unsort the inverse permutation, last[j] = len[j] - 1, all int32 [B] on the device.  tokens: int64 [B][seq_len] in CALLER order.
+ * No scratch; every element of every output is written (zeros included) unless said otherwise; no kernel here sums over slots.
+ *
+ * Layer-1 operand x:[t_max][B][E+S]: x[t][j] = [ table[tokens[order[j]][t]] * mask[t][j] | style[order[j]] ].  mask: the scaled
+ * keep-mask of dropout_in, [seq_len or t_max][B][E] in sorted order, or NULL.  A token outside [0, vocab) gives a NaN row. */
+int dwc_txt_operand_fwd(const float* table, const long long* tokens, const int* order, const float* mask, const float* style,
+                        float* x, int t_max, int B, int seq_len, int E, int S, int vocab, void* stream);
+/* Its adjoint as data movement, from dX = dxa + dxb (dxb NULL: dxa alone), both [t_max][B][E+S].  The outputs cover the FULL
+ * [seq_len][B] grid of slots (zeros for t >= t_max) and are the stock expression's own intermediate gradients -- values, shapes and
+ * strides --, so that the caller takes the two sums behind them with the reductions it used before and a run keeps its bits:
+ *   d_emb:[seq_len][B][E]    dX[t][j][:E] * mask[t][j], the gradient of the embedded tokens (sorted order); with
+ *   idx:[seq_len][B] int64   the token id of each slot, it is the input of the table's gradient (a sum per token id);
+ *   d_cat:[seq_len][B][E+S]  ONLY columns E.. are written: dX[t][j][E:] at row order[j] -- the gradient of the expanded style rows,
+ *                            in caller order, at the pitch of the concatenated operand; its sum over t is the style gradient.
+ * Each output may be NULL (a frozen table, a style that needs no gradient), not all three. */
+int dwc_txt_operand_bwd(const float* dxa, const float* dxb, const long long* tokens, const int* order, const float* mask,
+                        float* d_cat, float* d_emb, long long* idx, int t_max, int B, int seq_len, int E, int S, void* stream);
+/* The state entering each step, for the recurrent weight gradient of a layer: hprev[0][t] = out[0][t-1], hprev[1][t] = out[1][t+1],
+ * zeros at t = 0 / t = T-1; out, hprev:[2][T][B][H].  One launch instead of a zero fill and two shifted copies. */
+int dwc_txt_prev_state(const float* out, float* hprev, int T, int B, int H, void* stream);
+/* Between two layers: data[t][j][d*H+u] = out[d][t][j][u] * mask, out:[2][T][B][H].  mask NULL: none; mask_row NULL: mask is
+ * [T][B][2H]; else mask is [rows][2H] and slot (t, j) takes row mask_row[t*B+j] (int64: the packed-order draw of parity mode). */
+int dwc_txt_inter_fwd(const float* out, const float* mask, const long long* mask_row, float* data, int T, int B, int H, void* stream);
+/* d_out:[2][T][B][H] of layer `layer` (not the top one), written once: (dxa + dxb)[t][j][d*H+u] * mask -- the gradient coming
+ * down from the next layer's operand, [T][B][2H] -- plus the layer's final-state rows of d_feat (see dwc_txt_states_bwd). */
+int dwc_txt_inter_bwd(const float* dxa, const float* dxb, const float* mask, const long long* mask_row, const float* d_feat,
+                      const int* order, const int* last, int layer, float* d_out, int T, int B, int H, void* stream);
+/* Final states.  feat:[B][4*n*H], which read as [n][2B][2][H] holds for layer l, caller sample i and j = unsort[i]:
+ *   row i:     h = { out[l][0][last[j]][j], out[l][1][0][j] }        row B + i:  c, the same slots of c[l]
+ * (forward direction at the last token, reverse direction at t = 0; h_n and c_n concatenated along the BATCH axis and then viewed
+ * as (B, -1), which interleaves the samples of a batch exactly as reference networks_v2.py:249 does).  The struct travels by value. */
+#define DWC_TXT_MAX_LAYERS 4
+typedef struct dwc_txt_layers {
+    int n;                              /* layers, 1..DWC_TXT_MAX_LAYERS */
+    float* out[DWC_TXT_MAX_LAYERS];     /* [2][T][B][H] per layer (h_t; in the adjoint: its gradient, NULL = not written) */
+    float* c[DWC_TXT_MAX_LAYERS];       /* [2][T][B][H] per layer (cell state; in the adjoint: its gradient) */
+} dwc_txt_layers;
+int dwc_txt_states_fwd(dwc_txt_layers layers, const int* last, const int* unsort, float* feat, int T, int B, int H, void* stream);
+/* The adjoint: every non-NULL tensor of `grads` receives its rows of d_feat at the final-state slots and zeros everywhere else. */
+int dwc_txt_states_bwd(const float* d_feat, const int* order, const int* last, dwc_txt_layers grads, int T, int B, int H,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
