@@ -798,6 +798,174 @@ def ksplit_status_poll(wait=False):
             ent[1].record()
 
 
+# --------------------------------------------------------------------------------------
+# launchers of the convolution nodes: one per kernel family.  Each knows its family's prepared weight layout, scratch,
+# absmax slots, executed-flops factor, span and check tags and C argument order; WHICH family runs a layer is decided in the nodes.
+# ``B, H, W, Cx, cop``: the LAYER's geometry in both roles (Cx channels on x's side, cop on y's), handed over as integers -- reading
+# three tensor shapes costs more host time than the call.  ``shape`` / ``detail``: the span's problem-shape words, formatted once per
+# forward / backward.
+# --------------------------------------------------------------------------------------
+def _padded_bias(b, Cout, cop):
+    """The bias as the kernels read it: detached, zero-padded to the ``cop`` channels of the output buffer (None stays None)."""
+    if b is None:
+        return None
+    return (b.detach() if cop == Cout else torch.nn.functional.pad(b.detach(), (0, cop - Cout))).contiguous()
+
+
+def _splitk_ws(nws, dev):
+    """Scratch for the split-K partials of an im2col launch as the C ABI takes it: a pointer, or null where the plan does not split
+    (usually)."""
+    return workspace(nws, dev).data_ptr() if nws else None
+
+
+def _stem_bf16(half, planes, ch, KH, KW, stride, pad):
+    """bf16 7x7 stride-1 'same' convolution between an NHWC8 image and 64 channels, either way round (stem: image -> features, heads:
+    features -> image): the shape csrc/conv_narrow_bf16.hip's stem and small-K kernels are built for.  The caller adds the kernel's
+    own *_ok question."""
+    return half and NARROW and STEM and planes == 8 and ch == 64 and stride == 1 and KH == 7 and KW == 7 and pad == 3
+
+
+def _stem_x3(half, planes, ch, KH, KW, stride, pad):
+    """The fp32 twin on an NHWC4 image (csrc/conv_narrow_x3.hip); the caller adds its kernel's switch, NARROW_X3 or SMALLK_X3."""
+    return (not half) and X3 and planes == 4 and ch == 64 and stride == 1 and KH == 7 and KW == 7 and pad == 3
+
+
+def _sp_same(lib, src, w, owner, role, bias, add, dst, B, H, W, Cx, cop, K, act, reflect, flops, shape, what="", slot=False, at_least=0,
+             scope_name=None):
+    """Stride-1 'same' convolution of the fp32 ``src`` into ``dst`` as split products (csrc/conv_halo_x3.hip): two f16 planes where
+    h2_fits(src), else three bf16 planes.  ``role`` 'fwd': the filter as it stands; 'dgrad': rotated and transposed, src = dY (prepared
+    layouts h2_ / x3_ + role; the span's kind is the role).  ``add`` is summed into dst in the epilogue; ``slot``: dst gets an absmax
+    slot (the two-plane form raises it; nobody asks a three-plane result for one).  Small launches split their contraction: the arena
+    of the half sums, at least ``at_least`` bytes, is returned for a caller whose next launch shares it."""
+    c_in, c_out = (Cx, cop) if role == "fwd" else (cop, Cx)
+    st = _stream()
+    ws, ks_n, ks_t = _x3_ksplit(lib, src.device, B, H, W, c_in, c_out, K, 1, at_least)
+    if h2_fits(src):
+        w_p = _prepped(w, "h2_" + role, cop, Cx, 1, owner)
+        sa = amax_of(src)
+        da, dep = out_amax(dst) if slot else (None, 0)
+        _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_same_add_ws(
+            src.data_ptr(), sa[0], sa[1], w_p.data_ptr(), _p(bias), _p(add), dst.data_ptr(), da, dep, B, H, W, c_in, c_out, c_out, K, act,
+            reflect, _p(ws), ks_n, ks_t, st), scope_name=scope_name, detail=role + "-h2" + shape, exec_flops=3 * flops),
+            "h2_conv2d_same" + what)
+        if slot:
+            set_amax(dst, da, dep)
+    else:
+        w_p = _prepped(w, "x3_" + role, cop, Cx, 1, owner)
+        _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_same_add_ws(
+            src.data_ptr(), w_p.data_ptr(), _p(bias), _p(add), dst.data_ptr(), B, H, W, c_in, c_out, c_out, K, act, reflect, _p(ws), ks_n,
+            ks_t, st), scope_name=scope_name, detail=role + "-x3" + shape, exec_flops=6 * flops), "x3_conv2d_same" + what)
+    return ws
+
+
+def _halo_same_bf16(lib, src, w, owner, role, bias, add, dst, B, H, W, Cx, cop, K, act, reflect, flops, detail, what="", scope_name=None):
+    """Stride-1 'same' convolution of the bf16 ``src`` into ``dst`` on the halo-tiled kernel (csrc/conv_halo_bf16.hip: patch staged
+    once per channel slab), reading the im2col layout of its ``role``: 'fwd', or 'dgrad' with src = dY.  ``add`` is summed into dst
+    in the epilogue (null: dwc_bf16_conv2d_same_halo is this entry with add = nullptr)."""
+    c_in, c_out = (Cx, cop) if role == "fwd" else (cop, Cx)
+    w_p = _prepped(w, role, cop, Cx, 1, owner, True)
+    st = _stream()
+    _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_same_halo_add(
+        src.data_ptr(), w_p.data_ptr(), _p(bias), _p(add), dst.data_ptr(), B, H, W, c_in, c_out, K, act, reflect, st),
+        scope_name=scope_name, detail=detail), "conv2d_same_halo" + what)
+
+
+def _s2_dgrad_halo_ok(lib, half, B, H, W, Cx, cop, KH, KW, stride, pad):
+    """Whether the data gradient of this 4x4 stride-2 pad-1 layer runs in halo form: the shape, the size rule (S2DGRAD_MIN_WGS) and
+    the precision's kernel."""
+    return bool(S2DGRAD and stride == 2 and KH == 4 and KW == 4 and pad == 1
+                and 4 * B * (H // 32) * (W // 32) * (Cx // 64) >= S2DGRAD_MIN_WGS
+                and ((half and HALO and lib.dwc_bf16_conv2d_s2_halo_bwd_data_ok(B, H, W, Cx, cop))
+                     or ((not half) and X3 and lib.dwc_x3_conv2d_s2_bwd_data_ok(B, H, W, Cx, cop))))
+
+
+def _s2_dgrad_halo(lib, g, w, owner, dx, B, H, W, Cx, cop, flops, scope_name, shape, what=""):
+    """Data gradient of a 4x4 stride-2 layer as the four output-parity classes of 2x2-tap halo convolutions over dY: every pixel of
+    dx by the zero rule, i.e. the whole gradient under zero padding and the interior under reflect (the caller's ring launch adds the
+    border).  bf16 on the im2col 'dgrad' layout, fp32 as split products (two planes where h2_fits(g), else three)."""
+    st = _stream()
+    if g.dtype == BF16:
+        w_dg = _prepped(w, "dgrad", cop, Cx, 2, owner, True)
+        _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_s2_halo_bwd_data(
+            g.data_ptr(), w_dg.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, st), scope_name=scope_name,
+            detail="dgrad-s2halo" + shape), "conv2d_s2_halo_bwd_data" + what)
+    elif h2_fits(g):
+        w_h2 = _prepped(w, "h2_dgrad", cop, Cx, 1, owner)
+        ga = amax_of(g)
+        _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_s2_bwd_data(
+            g.data_ptr(), ga[0], ga[1], w_h2.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, Cx, st), scope_name=scope_name,
+            exec_flops=3 * flops, detail="dgrad-h2s2" + shape), "h2_conv2d_s2_bwd_data" + what)
+    else:
+        w_x3 = _prepped(w, "x3_dgrad", cop, Cx, 1, owner)
+        _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_s2_bwd_data(
+            g.data_ptr(), w_x3.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, Cx, st), scope_name=scope_name,
+            exec_flops=6 * flops, detail="dgrad-x3s2" + shape), "x3_conv2d_s2_bwd_data" + what)
+
+
+def _act_bwd(lib, dy, y, B, cop, Ho, Wo, act, need_db, slot=False):
+    """Gradient through the activation and the bias gradient in one pass over dY: (g, db_full).  g is dY itself when ``act`` is none;
+    db_full (one sum per channel of the padded buffer) is None unless ``need_db``.  ``slot``: g gets an absmax slot where out_amax
+    hands one out (dwc_act_bwd_bias_amax raises it while it writes g)."""
+    rows = B * Ho * Wo
+    dev = dy.device
+    db_full = torch.empty(cop, dtype=torch.float32, device=dev) if need_db else None
+    g_out = empty_cl(B, cop, Ho, Wo, dev, dy.dtype) if act != 0 else None
+    ws = workspace(lib.dwc_act_bwd_bias_ws_bytes(rows, cop), dev)
+    ga, gep = out_amax(g_out) if slot and g_out is not None else (None, 0)
+    if ga is not None:
+        _lib.check(lib.dwc_act_bwd_bias_amax(dy.data_ptr(), _p(y), g_out.data_ptr(), _p(db_full), rows, cop, act, ws.data_ptr(),
+                                             ws.numel(), ga, gep, _stream()), "act_bwd_bias")
+        set_amax(g_out, ga, gep)
+    else:
+        _lib.check(_fn(lib, "act_bwd_bias", dy)(dy.data_ptr(), _p(y), _p(g_out), _p(db_full), rows, cop, act, ws.data_ptr(),
+                                                ws.numel(), _stream()), "act_bwd_bias")
+    return (dy if g_out is None else g_out), db_full
+
+
+def _im2col_dgrad_reflect(lib, g, w, owner, dx, B, H, W, Cx, cop, KH, KW, stride, pad, flops, scope_name, detail):
+    """Data gradient through a reflect pad on the im2col GEMM ('dgrad' layout).  One scratch arena: [gradient of the padded image]
+    [split-K partials, usually none].  With DGRAD_FOLD the GEMM writes the interior straight into dx and only the border ring goes
+    through the padded scratch (GEMM + reflect-pad adjoint in one call); else the whole padded image does and reflect_pad_adjoint
+    folds it back.  pad 0: the GEMM's result is dx."""
+    half = g.dtype == BF16
+    st = _stream()
+    w_dg = _prepped(w, "dgrad", cop, Cx, stride, owner, half)
+    pad_bytes = 0 if pad == 0 else (B * (H + 2 * pad) * (W + 2 * pad) * Cx * (2 if half else 4) + 255) // 256 * 256
+    nws = _fn(lib, "conv2d_bwd_data_ws_bytes", g)(B, H, W, Cx, cop, KH, KW, stride, pad)
+    base = workspace(pad_bytes + nws, g.device).data_ptr() if pad_bytes + nws else 0
+    wsp = base + pad_bytes if nws else None
+    if pad > 0 and DGRAD_FOLD and min(H, W) >= 2 * pad + 2 and Cx % (8 if half else 4) == 0:
+        _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data_fold", g)(
+            g.data_ptr(), w_dg.data_ptr(), base, dx.data_ptr(), B, H, W, Cx, cop, KH, KW, stride, pad, wsp, nws, st),
+            scope_name=scope_name, detail=detail), "conv2d_bwd_data_fold")
+    else:
+        target = dx.data_ptr() if pad == 0 else base
+        _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data", g)(
+            g.data_ptr(), w_dg.data_ptr(), target, B, H, W, Cx, cop, KH, KW, stride, pad, wsp, nws, st),
+            scope_name=scope_name, detail=detail), "conv2d_bwd_data")
+        if pad > 0:
+            _lib.check(_fn(lib, "reflect_pad_adjoint", g)(target, dx.data_ptr(), B, H, W, Cx, pad, st), "reflect_pad_adjoint")
+
+
+def _smallk_wgrad(lib, x, g, dw, B, H, W, planes, swapped, flops, scope_name, kind, shape):
+    """7x7 weight gradient between an image buffer and 64 channels on the small-K kernels (csrc/conv_narrow_bf16.hip: 4 taps x 8
+    planes per MFMA row tile; csrc/conv_narrow_x3.hip smallk_wgrad_x3_kernel: one filter row of 8 taps x 4 planes, split products).
+    Stem: A = the image x, Bt = dY, Cin real planes.  ``swapped`` (image heads): the roles exchanged -- A = the gradient image, Bt = x on
+    the padded grid, Cout real planes."""
+    a, bt = (g, x) if swapped else (x, g)
+    st = _stream()
+    if x.dtype == BF16:
+        ws = workspace(lib.dwc_bf16_conv7_smallk_wgrad_ws_bytes(B, H, W, int(swapped)), x.device)
+        _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: lib.dwc_bf16_conv7_smallk_wgrad(
+            a.data_ptr(), bt.data_ptr(), dw.data_ptr(), B, H, W, planes, int(swapped), ws.data_ptr(), ws.numel(), st),
+            scope_name=scope_name, detail=kind + shape), "conv7_smallk_wgrad")
+    else:
+        ws = workspace(lib.dwc_x3_conv7_smallk_wgrad_ws_bytes(B, H, W, int(swapped)), x.device)
+        _lib.check(_timed("wgrad_x3_kernel+reduce", flops, lambda: lib.dwc_x3_conv7_smallk_wgrad(
+            a.data_ptr(), bt.data_ptr(), dw.data_ptr(), B, H, W, planes, int(swapped), ws.data_ptr(), ws.numel(), st),
+            scope_name=scope_name, detail=kind + "-x3" + shape, exec_flops=6 * flops), "x3_conv7_smallk_wgrad")
+
+
 class _Conv2d(torch.autograd.Function):
     """act(conv(pad(x)) + b), the padding rule inside the kernels' gather.  Output has Cout rounded up to a multiple of 4 (fp32) /
     8 (bf16); its dtype is x's.
@@ -837,34 +1005,15 @@ class _Conv2d(torch.autograd.Function):
         # 200 us on 64 workgroups against 118 us on the native kernel)
         use_x3s2 = bool((not half) and X3 and X3_S2 and stride == 2 and KH == 4 and KW == 4 and pad == 1 and cop % 64 == 0
                         and B * (H // 32) * (W // 32) * (cop // 64) >= 160 and lib.dwc_x3_conv2d_s2_ok(B, H, W, Cx, cop))
-        use_stem = bool(half and NARROW and STEM and Cx == 8 and cop == 64 and stride == 1 and KH == 7 and KW == 7 and pad == 3
-                        and lib.dwc_bf16_conv2d_stem_ok(B, H, W, H, W, KH, act))
-        use_stem_x3 = bool((not half) and X3 and NARROW_X3 and Cx == 4 and cop == 64 and stride == 1 and KH == 7 and KW == 7 and pad == 3
-                           and lib.dwc_x3_conv2d_stem_ok(B, H, W, H, W, KH, act))
-        w_hwio = None if use_x3 or use_x3s2 or use_stem or use_stem_x3 else _prepped(w, "fwd", cop, Cx, stride, owner, half)
-        bias = None
-        if b is not None:
-            bias = b.detach() if cop == Cout else torch.nn.functional.pad(b.detach(), (0, cop - Cout))
-            bias = bias.contiguous()
+        use_stem = bool(_stem_bf16(half, Cx, cop, KH, KW, stride, pad) and lib.dwc_bf16_conv2d_stem_ok(B, H, W, H, W, KH, act))
+        use_stem_x3 = bool(NARROW_X3 and _stem_x3(half, Cx, cop, KH, KW, stride, pad) and lib.dwc_x3_conv2d_stem_ok(B, H, W, H, W, KH, act))
+        bias = _padded_bias(b, Cout, cop)
         y = empty_cl(B, cop, Ho, Wo, x.device, x.dtype)
         flops = 2.0 * B * Ho * Wo * Cout * Cin * KH * KW
         st = _stream()
-        if use_x3 and h2_fits(x):
-            w_h2 = _prepped(w, "h2_fwd", cop, Cx, 1, owner)
-            ks_ws, ks_n, ks_t = _x3_ksplit(lib, x.device, B, H, W, Cx, cop, KH, 1)
-            x_amax = amax_of(x)
-            ya, yep = out_amax(y)
-            _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_same_add_ws(
-                x.data_ptr(), x_amax[0], x_amax[1], w_h2.data_ptr(), _p(bias), None, y.data_ptr(), ya, yep, B, H, W, Cx, cop, cop, KH, act, refl,
-                _p(ks_ws), ks_n, ks_t, st), detail="fwd-h2 B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride), exec_flops=3 * flops),
-                "h2_conv2d_same")
-            set_amax(y, ya, yep)
-        elif use_x3:
-            w_x3 = _prepped(w, "x3_fwd", cop, Cx, 1, owner)
-            ks_ws, ks_n, ks_t = _x3_ksplit(lib, x.device, B, H, W, Cx, cop, KH, 1)
-            _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_same_add_ws(
-                x.data_ptr(), w_x3.data_ptr(), _p(bias), None, y.data_ptr(), B, H, W, Cx, cop, cop, KH, act, refl, _p(ks_ws), ks_n, ks_t, st),
-                detail="fwd-x3 B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride), exec_flops=6 * flops), "x3_conv2d_same")
+        shape = " B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)
+        if use_x3:
+            _sp_same(lib, x, w, owner, "fwd", bias, None, y, B, H, W, Cx, cop, KH, act, refl, flops, shape, slot=True)
         elif use_x3s2 and h2_fits(x):
             w_h2 = _prepped(w, "h2_fwd", cop, Cx, 1, owner)
             ks_ws, ks_n, ks_t = _x3_ksplit(lib, x.device, B, H, W, Cx, cop, KH, 2)
@@ -872,7 +1021,7 @@ class _Conv2d(torch.autograd.Function):
             ya, yep = out_amax(y)
             _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: getattr(lib, "dwc_h2_conv2d_s2_ws" + z)(
                 x.data_ptr(), x_amax[0], x_amax[1], w_h2.data_ptr(), _p(bias), y.data_ptr(), ya, yep, B, H, W, Cx, cop, cop, act, _p(ks_ws), ks_n,
-                ks_t, st), detail="fwd-h2s2 B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride), exec_flops=3 * flops), "h2_conv2d_s2")
+                ks_t, st), detail="fwd-h2s2" + shape, exec_flops=3 * flops), "h2_conv2d_s2")
             set_amax(y, ya, yep)
         elif use_x3s2:
             # stride-2 4x4 layers, fp32: split products, 2x2 taps per input-pixel parity, space-to-depth in the patch gather
@@ -880,14 +1029,14 @@ class _Conv2d(torch.autograd.Function):
             ks_ws, ks_n, ks_t = _x3_ksplit(lib, x.device, B, H, W, Cx, cop, KH, 2)
             _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: getattr(lib, "dwc_x3_conv2d_s2_ws" + z)(
                 x.data_ptr(), w_x3.data_ptr(), _p(bias), y.data_ptr(), B, H, W, Cx, cop, cop, act, _p(ks_ws), ks_n, ks_t, st),
-                detail="fwd-x3s2 B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride), exec_flops=6 * flops), "x3_conv2d_s2")
+                detail="fwd-x3s2" + shape, exec_flops=6 * flops), "x3_conv2d_s2")
         elif use_stem_x3:
             # fp32 7x7 stem on an NHWC4 image as split products: filter planes resident in LDS, persistent workgroups (csrc/conv_narrow_x3.hip)
             w_st = _prepped(w, "stem_steps_x3", cop, Cx, 1, owner)
             ya, yep = out_amax(y)                     # (the stride-2 layer behind the stem is a two-plane kernel: it wants y's absmax)
             _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_stem_amax(
                 x.data_ptr(), w_st.data_ptr(), _p(bias), y.data_ptr(), ya, yep, B, H, W, H, W, KH, -pad, act, refl, st),
-                detail="fwd-stem-x3 B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride), exec_flops=6 * flops), "x3_conv2d_stem")
+                detail="fwd-stem-x3" + shape, exec_flops=6 * flops), "x3_conv2d_stem")
             if ya is not None:
                 set_amax(y, ya, yep)
         elif use_stem:
@@ -895,24 +1044,24 @@ class _Conv2d(torch.autograd.Function):
             w_st = _prepped(w, "stem_steps", cop, Cx, 1, owner, True)
             _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_stem(
                 x.data_ptr(), w_st.data_ptr(), _p(bias), y.data_ptr(), B, H, W, H, W, KH, -pad, act, refl, st),
-                detail="fwd-stem B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)), "conv2d_stem")
+                detail="fwd-stem" + shape), "conv2d_stem")
         elif (half and HALO and S2HALO and stride == 2 and KH == 4 and KW == 4 and pad == 1
               and lib.dwc_bf16_conv2d_s2_halo_ok(B, H, W, Cx, cop)):
             # stride-2 4x4 layers on the bf16 path: 2x2 taps over the space-to-depth image, space-to-depth done by the loader
+            w_hwio = _prepped(w, "fwd", cop, Cx, stride, owner, True)
             _lib.check(_timed("conv_gemm_kernel", flops, lambda: getattr(lib, "dwc_bf16_conv2d_s2_halo" + z)(
                 x.data_ptr(), w_hwio.data_ptr(), _p(bias), y.data_ptr(), B, H, W, Cx, cop, act, st),
-                detail="fwd-s2halo B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)), "conv2d_s2_halo")
+                detail="fwd-s2halo" + shape), "conv2d_s2_halo")
         elif half and HALO and stride == 1 and KH == KW and 2 * pad == KH - 1 and lib.dwc_bf16_conv2d_same_halo_ok(B, H, W, Cx, cop, KH):
-            # stride-1 "same" 3x3 / 5x5 layers on the bf16 path: halo-tiled kernel (patch staged once per channel slab)
-            _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_same_halo(
-                x.data_ptr(), w_hwio.data_ptr(), _p(bias), y.data_ptr(), B, H, W, Cx, cop, KH, act, refl, st),
-                detail="fwd-halo B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)), "conv2d_same_halo")
+            # stride-1 "same" 3x3 / 5x5 layers on the bf16 path
+            _halo_same_bf16(lib, x, w, owner, "fwd", bias, None, y, B, H, W, Cx, cop, KH, act, refl, flops, "fwd-halo" + shape)
         else:
+            w_hwio = _prepped(w, "fwd", cop, Cx, stride, owner, half)
             nws = _fn(lib, "conv2d_fwd_ws_bytes", x)(B, H, W, Cx, cop, KH, KW, stride, pad)     # split-K partials, usually 0
-            wsp = workspace(nws, x.device).data_ptr() if nws else None
+            wsp = _splitk_ws(nws, x.device)
             _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_fwd_zeropad" if zero else "conv2d_fwd", x)(
                 x.data_ptr(), w_hwio.data_ptr(), _p(bias), y.data_ptr(), B, H, W, Cx, cop, KH, KW, stride, pad, act, wsp, nws,
-                st), detail="fwd B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)), "conv2d_fwd")
+                st), detail="fwd" + shape), "conv2d_fwd")
         ctx.save_for_backward(x, w, y if act != 0 else None)
         ctx.x_amax = getattr(x, "_dwc_amax", None)        # (slot, epoch, version, address) if something measured x (two-plane kernels)
         ctx.geom = (B, H, W, Cx, cop, KH, KW, stride, pad, act, Cin, Cout, b is not None)
@@ -924,14 +1073,8 @@ class _Conv2d(torch.autograd.Function):
         lib = _lib.load()
         x, w, y = ctx.saved_tensors
         B, H, W, Cx, cop, KH, KW, stride, pad, act, Cin, Cout, has_b = ctx.geom
-        owner = ctx.owner
-        dt = x.dtype
-        half = dt == BF16
         dy = cl(dy)
         Ho, Wo = dy.shape[2], dy.shape[3]
-        rows = B * Ho * Wo
-        st = _stream()
-        dev = x.device
         need_db = has_b and ctx.needs_input_grad[2]
         g = dy
         db = None
@@ -940,106 +1083,99 @@ class _Conv2d(torch.autograd.Function):
             # subtraction, so this gradient is identically zero (the reference computes rounding noise here).  The parameter carries
             # `_dwc_zero_grad` (set in forward): FusedAdam steps it with a shared zero vector, the data-parallel reducer does not wait for
             # it -- no gradient tensor, no fill launch (r05: 38 per iteration).  Anything else asks for a real zero tensor.
-            db, need_db = (None if ctx.zero_flag else torch.zeros(Cout, dtype=torch.float32, device=dev)), False
+            db, need_db = (None if ctx.zero_flag else torch.zeros(Cout, dtype=torch.float32, device=x.device)), False
         if act != 0 or need_db:
-            db_full = torch.empty(cop, dtype=torch.float32, device=dev) if need_db else None
-            g_out = empty_cl(B, cop, Ho, Wo, dev, dt) if act != 0 else None
-            nws = lib.dwc_act_bwd_bias_ws_bytes(rows, cop)
-            ws = workspace(nws, dev)
-            ga_, gep_ = out_amax(g_out) if g_out is not None else (None, 0)
-            if ga_ is not None:
-                _lib.check(lib.dwc_act_bwd_bias_amax(dy.data_ptr(), _p(y), _p(g_out), _p(db_full), rows, cop, act, ws.data_ptr(),
-                                                     ws.numel(), ga_, gep_, st), "act_bwd_bias")
-                set_amax(g_out, ga_, gep_)
-            else:
-                _lib.check(_fn(lib, "act_bwd_bias", x)(dy.data_ptr(), _p(y), _p(g_out), _p(db_full), rows, cop, act, ws.data_ptr(),
-                                                       ws.numel(), st), "act_bwd_bias")
-            _hbm("act_bwd_bias", dy.numel() * dy.element_size() * ((1 if y is None else 2) + (1 if g_out is not None else 0)))
-            if g_out is not None:
-                g = g_out
+            g, db_full = _act_bwd(lib, dy, y, B, cop, Ho, Wo, act, need_db, slot=True)
+            _hbm("act_bwd_bias", dy.numel() * dy.element_size() * ((1 if y is None else 2) + (1 if act != 0 else 0)))
             if need_db:
                 db = db_full[:Cout]
-        dx = dw = None
         # identity-branch gradient of the residual block this convolution opens (ResGradToken), channels-last like dx
         g_res = None
         if ctx.token is not None:
             g_res, ctx.token.g = ctx.token.g, None
             if g_res is not None:
                 g_res = cl(g_res)
-                if g_res.shape[1] != Cx or g_res.dtype != dt or not ctx.needs_input_grad[0]:
+                if g_res.shape[1] != Cx or g_res.dtype != x.dtype or not ctx.needs_input_grad[0]:
                     raise RuntimeError("residual-gradient token: shape / dtype of the identity branch does not match the block input")
-        pow2 = (cop & (cop - 1)) == 0
-        zero = ctx.zero
+        flops = 2.0 * B * Ho * Wo * Cout * Cin * KH * KW
+        shape = " B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)
+        dx = dw = None
         if ctx.needs_input_grad[1]:
-            dw = torch.empty((Cout, Cin, KH, KW), dtype=torch.float32, device=dev)
-            flops = 2.0 * rows * Cout * Cin * KH * KW
-            detail = "wgrad B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)
-            # zero rule: the halo kernels' and the im2col kernel's zero-rule instantiations, by the same size rules, plans and scratch as
-            # under reflect (z); the small-K 7x7 kernels stage their patches by the reflect rule and leave those layers to im2col
-            z = "_zeropad" if zero else ""
-            if (not zero) and half and NARROW and STEM and Cx == 8 and cop == 64 and stride == 1 and KH == 7 and KW == 7 and pad == 3 and Cout == 64:
-                # 7x7 stem on an NHWC8 image: 4 taps x 8 planes per MFMA row tile (csrc/conv_narrow_bf16.hip)
-                ws = workspace(lib.dwc_bf16_conv7_smallk_wgrad_ws_bytes(B, H, W, 0), dev)
-                _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: lib.dwc_bf16_conv7_smallk_wgrad(
-                    x.data_ptr(), g.data_ptr(), dw.data_ptr(), B, H, W, Cin, 0, ws.data_ptr(), ws.numel(), st),
-                    scope_name=ctx.bscope, detail="wgrad-stem" + detail[5:]), "conv7_smallk_wgrad")
-            elif ((not zero) and (not half) and X3 and SMALLK_X3 and Cx == 4 and cop == 64 and stride == 1 and KH == 7 and KW == 7 and pad == 3
-                  and Cout == 64):
-                # fp32 7x7 stem on an NHWC4 image: one filter row (8 taps x 4 planes) per MFMA row tile, split products
-                # (csrc/conv_narrow_x3.hip smallk_wgrad_x3_kernel)
-                ws = workspace(lib.dwc_x3_conv7_smallk_wgrad_ws_bytes(B, H, W, 0), dev)
-                _lib.check(_timed("wgrad_x3_kernel+reduce", flops, lambda: lib.dwc_x3_conv7_smallk_wgrad(
-                    x.data_ptr(), g.data_ptr(), dw.data_ptr(), B, H, W, Cin, 0, ws.data_ptr(), ws.numel(), st),
-                    scope_name=ctx.bscope, detail="wgrad-stem-x3" + detail[5:], exec_flops=6 * flops), "x3_conv7_smallk_wgrad")
-            elif ((not half) and (_x3_use(lib, B, H, W, Cx, cop, KH, KW, stride, pad)
-                                  or (X3 and X3_S2 and stride == 2 and KH == 4 and KW == 4 and pad == 1))
-                  and (KH != 3 or X3_WGRAD_HALO3) and (not zero or B * H * W * Cx * 4 < (1 << 31))
-                  and lib.dwc_x3_conv2d_wgrad_ws_bytes(B, H, W, Cx, cop, KH)):
-                ws = workspace(lib.dwc_x3_conv2d_wgrad_ws_bytes(B, H, W, Cx, cop, KH), dev)
-                if X3_PLANES == 2:
-                    xa = amax_live(x, ctx.x_amax) or amax_of(x)          # the forward's measurement if it still stands
-                    ga = amax_of(g)
-                    _lib.check(_timed("wgrad_x3_kernel+reduce", flops, lambda: getattr(lib, "dwc_h2_conv2d_wgrad" + z)(
-                        x.data_ptr(), xa[0], xa[1], g.data_ptr(), ga[0], ga[1], dw.data_ptr(), B, H, W, Cx, cop, KH, Cin, Cout, ws.data_ptr(),
-                        ws.numel(), st), scope_name=ctx.bscope, detail="wgrad-h2" + detail[5:], exec_flops=3 * flops), "h2_conv2d_wgrad" + z)
-                else:
-                    _lib.check(_timed("wgrad_x3_kernel+reduce", flops, lambda: getattr(lib, "dwc_x3_conv2d_wgrad" + z)(
-                        x.data_ptr(), g.data_ptr(), dw.data_ptr(), B, H, W, Cx, cop, KH, Cin, Cout, ws.data_ptr(), ws.numel(), st),
-                        scope_name=ctx.bscope, detail="wgrad-x3" + detail[5:], exec_flops=6 * flops), "x3_conv2d_wgrad" + z)
-            elif (half and WGRAD_HALO and KH == KW and ((stride == 1 and KH in (3, 5) and 2 * pad == KH - 1)
-                                                         or (S2HALO and stride == 2 and KH == 4 and pad == 1))
-                  and lib.dwc_bf16_conv2d_wgrad_halo_ws_bytes(B, H, W, Cx, cop, KH)):
-                ws = workspace(lib.dwc_bf16_conv2d_wgrad_halo_ws_bytes(B, H, W, Cx, cop, KH), dev)
-                _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: getattr(lib, "dwc_bf16_conv2d_wgrad_halo" + z)(
-                    x.data_ptr(), g.data_ptr(), dw.data_ptr(), B, H, W, Cx, cop, KH, Cin, Cout, ws.data_ptr(), ws.numel(), st),
-                    scope_name=ctx.bscope, detail="wgrad-halo" + detail[5:]), "conv2d_wgrad_halo" + z)
-            else:
-                nws = _fn(lib, "conv2d_bwd_weight_ws_bytes", x)(B, H, W, Cx, cop, KH, KW, stride, pad)
-                ws = workspace(nws, dev)
-                _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: _fn(lib, "conv2d_bwd_weight" + z, x)(
-                    x.data_ptr(), g.data_ptr(), dw.data_ptr(), B, H, W, Cx, cop, KH, KW, stride, pad, Cin, Cout, ws.data_ptr(),
-                    ws.numel(), st), scope_name=ctx.bscope, detail=detail), "conv2d_bwd_weight" + z)
-        same = stride == 1 and pad > 0 and 2 * pad == KH - 1 and KH == KW and cop >= 32 and pow2
-        if ctx.needs_input_grad[0] and zero:
-            dx, used = _Conv2d._zero_dgrad_halo(ctx, lib, g, g_res, w, same)      # None: no halo kernel takes the shape (below)
+            dw = _Conv2d._wgrad(ctx, lib, x, g, w, flops, shape)
+        if ctx.needs_input_grad[0]:
+            # (a stride-1 'same' layer whose gathered channel count the data-gradient kernels' interior forms take)
+            same = stride == 1 and pad > 0 and 2 * pad == KH - 1 and KH == KW and cop >= 32 and (cop & (cop - 1)) == 0
+            dx, used = (_Conv2d._dgrad_zero if ctx.zero else _Conv2d._dgrad_reflect)(ctx, lib, g, g_res, w, same, flops, shape)
             if used:
                 g_res = None                                   # consumed by the kernel's epilogue
-        if dx is not None:
-            pass
-        elif ctx.needs_input_grad[0] and (not zero) and Cx == image_planes(dt) and same:
+        if g_res is not None and dx is not None:               # no fused form on this path: the plain sum
+            dx = dx + g_res.to(dx.dtype)
+        return dx, dw, db, None, None, None, None, None, None, None, None
+
+    @staticmethod
+    def _wgrad(ctx, lib, x, g, w, flops, shape):
+        """Weight gradient: the 7x7 stems on the small-K kernels, 3x3 / 5x5 / stride-2 4x4 on the halo kernels, else the im2col GEMM."""
+        B, H, W, Cx, cop, KH, KW, stride, pad, act, Cin, Cout, has_b = ctx.geom
+        half = x.dtype == BF16
+        dev, st = x.device, _stream()
+        zero = ctx.zero
+        dw = torch.empty((Cout, Cin, KH, KW), dtype=torch.float32, device=dev)
+        # zero rule: the halo kernels' and the im2col kernel's zero-rule instantiations, by the same size rules, plans and scratch as
+        # under reflect (z); the small-K 7x7 kernels stage their patches by the reflect rule and leave those layers to im2col
+        z = "_zeropad" if zero else ""
+        if (not zero) and Cout == 64 and (_stem_bf16(half, Cx, cop, KH, KW, stride, pad)
+                                          or (SMALLK_X3 and _stem_x3(half, Cx, cop, KH, KW, stride, pad))):
+            _smallk_wgrad(lib, x, g, dw, B, H, W, Cin, False, flops, ctx.bscope, "wgrad-stem", shape)
+        elif ((not half) and (_x3_use(lib, B, H, W, Cx, cop, KH, KW, stride, pad)
+                              or (X3 and X3_S2 and stride == 2 and KH == 4 and KW == 4 and pad == 1))
+              and (KH != 3 or X3_WGRAD_HALO3) and (not zero or B * H * W * Cx * 4 < (1 << 31))
+              and lib.dwc_x3_conv2d_wgrad_ws_bytes(B, H, W, Cx, cop, KH)):
+            ws = workspace(lib.dwc_x3_conv2d_wgrad_ws_bytes(B, H, W, Cx, cop, KH), dev)
+            if X3_PLANES == 2:
+                xa = amax_live(x, ctx.x_amax) or amax_of(x)          # the forward's measurement if it still stands
+                ga = amax_of(g)
+                _lib.check(_timed("wgrad_x3_kernel+reduce", flops, lambda: getattr(lib, "dwc_h2_conv2d_wgrad" + z)(
+                    x.data_ptr(), xa[0], xa[1], g.data_ptr(), ga[0], ga[1], dw.data_ptr(), B, H, W, Cx, cop, KH, Cin, Cout, ws.data_ptr(),
+                    ws.numel(), st), scope_name=ctx.bscope, detail="wgrad-h2" + shape, exec_flops=3 * flops), "h2_conv2d_wgrad" + z)
+            else:
+                _lib.check(_timed("wgrad_x3_kernel+reduce", flops, lambda: getattr(lib, "dwc_x3_conv2d_wgrad" + z)(
+                    x.data_ptr(), g.data_ptr(), dw.data_ptr(), B, H, W, Cx, cop, KH, Cin, Cout, ws.data_ptr(), ws.numel(), st),
+                    scope_name=ctx.bscope, detail="wgrad-x3" + shape, exec_flops=6 * flops), "x3_conv2d_wgrad" + z)
+        elif (half and WGRAD_HALO and KH == KW and ((stride == 1 and KH in (3, 5) and 2 * pad == KH - 1)
+                                                     or (S2HALO and stride == 2 and KH == 4 and pad == 1))
+              and lib.dwc_bf16_conv2d_wgrad_halo_ws_bytes(B, H, W, Cx, cop, KH)):
+            ws = workspace(lib.dwc_bf16_conv2d_wgrad_halo_ws_bytes(B, H, W, Cx, cop, KH), dev)
+            _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: getattr(lib, "dwc_bf16_conv2d_wgrad_halo" + z)(
+                x.data_ptr(), g.data_ptr(), dw.data_ptr(), B, H, W, Cx, cop, KH, Cin, Cout, ws.data_ptr(), ws.numel(), st),
+                scope_name=ctx.bscope, detail="wgrad-halo" + shape), "conv2d_wgrad_halo" + z)
+        else:
+            nws = _fn(lib, "conv2d_bwd_weight_ws_bytes", x)(B, H, W, Cx, cop, KH, KW, stride, pad)
+            ws = workspace(nws, dev)
+            _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: _fn(lib, "conv2d_bwd_weight" + z, x)(
+                x.data_ptr(), g.data_ptr(), dw.data_ptr(), B, H, W, Cx, cop, KH, KW, stride, pad, Cin, Cout, ws.data_ptr(),
+                ws.numel(), st), scope_name=ctx.bscope, detail="wgrad" + shape), "conv2d_bwd_weight" + z)
+        return dw
+
+    @staticmethod
+    def _dgrad_reflect(ctx, lib, g, g_res, w, same, flops, shape):
+        """Data gradient through a reflect pad: (dx, whether g_res was added in a kernel's epilogue)."""
+        B, H, W, Cx, cop, KH, KW, stride, pad, act, Cin, Cout, has_b = ctx.geom
+        owner = ctx.owner
+        dt = g.dtype
+        half = dt == BF16
+        dev, st = g.device, _stream()
+        dx = empty_cl(B, Cx, H, W, dev, dt)
+        if Cx == image_planes(dt) and same:
             # gradient w.r.t. an NHWC4 / NHWC8 image (7x7 stems): 32/Cx pixels x Cx planes per GEMM row,
             # see dwc_conv2d_bwd_data_image
-            dx = empty_cl(B, Cx, H, W, dev, dt)
-            flops = 2.0 * rows * Cout * Cin * KH * KW
-            nws = _fn(lib, "conv2d_bwd_data_image_ws_bytes", x)(B, H, W, cop, KH, KW, pad)
+            nws = _fn(lib, "conv2d_bwd_data_image_ws_bytes", g)(B, H, W, cop, KH, KW, pad)
             ws = workspace(nws, dev)
             wg4 = (W + 2 * pad + 3) // 4
             if half and NARROW and lib.dwc_bf16_conv2d_narrow_ok(B, H, W, cop, H + 2 * pad, wg4, KH, KW + 3):
                 w_frag = _prepped(w, "dgrad_image_narrow", cop, Cx, 1, owner, True)
                 _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_bwd_data_image_narrow(
                     g.data_ptr(), w_frag.data_ptr(), dx.data_ptr(), B, H, W, cop, KH, KW, pad, ws.data_ptr(), ws.numel(), st),
-                    scope_name=ctx.bscope, detail="dgrad-image-narrow B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)),
-                    "conv2d_bwd_data_image_narrow")
+                    scope_name=ctx.bscope, detail="dgrad-image-narrow" + shape), "conv2d_bwd_data_image_narrow")
             elif ((not half) and X3 and NARROW_X3 and Cx == 4 and cop == 64
                   and lib.dwc_x3_conv2d_narrow_ok(B, H, W, cop, H + 2 * pad, (W + 2 * pad + 7) // 8, KH, KW + 7)):
                 # fp32: the padded gradient image on the split-product narrow kernel (zero rule), folded by the reflect adjoint
@@ -1047,221 +1183,117 @@ class _Conv2d(torch.autograd.Function):
                 w_frag = _prepped(w, "dgrad_image_narrow_x3", cop, Cx, 1, owner)
                 _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_narrow(
                     g.data_ptr(), w_frag.data_ptr(), None, ws.data_ptr(), B, H, W, cop, H + 2 * pad, wg8, KH, KW + 7, -(KH - 1), -(KW - 1),
-                    0, 0, st), scope_name=ctx.bscope, exec_flops=6 * flops,
-                    detail="dgrad-image-nx3 B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)), "x3_conv2d_narrow dgrad")
+                    0, 0, st), scope_name=ctx.bscope, exec_flops=6 * flops, detail="dgrad-image-nx3" + shape), "x3_conv2d_narrow dgrad")
                 _lib.check(lib.dwc_reflect_pad_adjoint_pitch(ws.data_ptr(), dx.data_ptr(), B, H, W, Cx, pad, 8 * wg8, st),
                            "reflect_pad_adjoint_pitch")
             else:
                 w_img = _prepped(w, "dgrad_image", cop, Cx, 1, owner, half)
-                _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data_image", x)(
+                _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data_image", g)(
                     g.data_ptr(), w_img.data_ptr(), dx.data_ptr(), B, H, W, cop, KH, KW, pad, ws.data_ptr(), ws.numel(), st),
-                    scope_name=ctx.bscope, detail="dgrad-image B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)),
-                    "conv2d_bwd_data_image")
-        elif ctx.needs_input_grad[0] and (not zero) and same and min(H, W) >= 2 * pad + 2 and (not half or cop >= 64):
+                    scope_name=ctx.bscope, detail="dgrad-image" + shape), "conv2d_bwd_data_image")
+            return dx, False
+        if same and min(H, W) >= 2 * pad + 2 and (not half or cop >= 64):
             # "same" convolutions: interior on the H x W grid straight into dx + the thin border ring (no padded image)
             w_dg = lambda: _prepped(w, "dgrad", cop, Cx, 1, owner, half).data_ptr()        # (lazily: the fused fp32 form reads neither)
             w_dg_t = lambda: _prepped(w, "dgrad_t", cop, Cx, 1, owner, half).data_ptr()     # (only the strip GEMMs of the ring read it)
-            dx = empty_cl(B, Cx, H, W, dev, dt)
-            flops = 2.0 * rows * Cout * Cin * KH * KW
-            nws = _fn(lib, "conv2d_bwd_data_same_ws_bytes", x)(B, H, W, Cx, cop, KH, KW, pad)
-            x3 = (not half) and _x3_use(lib, B, H, W, cop, Cx, KH, KW, stride, pad, free=True)
-            if x3:
+            nws = _fn(lib, "conv2d_bwd_data_same_ws_bytes", g)(B, H, W, Cx, cop, KH, KW, pad)
+            # (two spans: the interior launch carries the layer's flops, the ring strips + fold are time on top of it)
+            if (not half) and _x3_use(lib, B, H, W, cop, Cx, KH, KW, stride, pad, free=True):
                 # interior = zero-padded convolution of dY with the rotated filter on the split-product kernel; ring direct
-                w_x3 = _prepped(w, "x3_dgrad", cop, Cx, 1, owner) if not h2_fits(g) else None
-                # (one arena: the interior's half sums -- small launches, contraction split -- are dead when the ring strips start)
-                fused = bool(RING_FUSED and h2_fits(g) and min(H, W) >= 32)
-                ws, ks_n, ks_t = _x3_ksplit(lib, dev, B, H, W, cop, Cx, KH, 1, at_least=0 if fused else nws)
-
-                shape = " B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)
-                # (two spans: the interior launch carries the layer's flops, the ring strips + fold are time on top of it)
-                if fused:
+                if RING_FUSED and h2_fits(g) and min(H, W) >= 32:
                     # interior AND border ring in one launch: border tiles read pre-summed patch pixels (r06, conv_halo_x3_kernel RING)
+                    ws, ks_n, ks_t = _x3_ksplit(lib, dev, B, H, W, cop, Cx, KH, 1)
                     w_h2 = _prepped(w, "h2_dgrad", cop, Cx, 1, owner)
                     ga = amax_of(g)
                     _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_bwd_data_same_fused(
                         g.data_ptr(), ga[0], ga[1], w_h2.data_ptr(), _p(g_res), dx.data_ptr(), B, H, W, cop, Cx, Cx, KH,
                         _p(ws), ks_n, ks_t, st), scope_name=ctx.bscope, exec_flops=3 * flops, detail="dgrad-h2" + shape),
                         "h2_conv2d_bwd_data_same_fused")
-                elif h2_fits(g):
-                    w_h2 = _prepped(w, "h2_dgrad", cop, Cx, 1, owner)
-                    ga = amax_of(g)
-                    _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_same_add_ws(
-                        g.data_ptr(), ga[0], ga[1], w_h2.data_ptr(), None, _p(g_res), dx.data_ptr(), None, 0, B, H, W, cop, Cx, Cx, KH, 0, 0,
-                        ws.data_ptr(), ks_n, ks_t, st), scope_name=ctx.bscope, exec_flops=3 * flops, detail="dgrad-h2" + shape),
-                        "h2_conv2d_same dgrad")
-                else:
-                    _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_same_add_ws(
-                        g.data_ptr(), w_x3.data_ptr(), None, _p(g_res), dx.data_ptr(), B, H, W, cop, Cx, Cx, KH, 0, 0, ws.data_ptr(), ks_n,
-                        ks_t, st), scope_name=ctx.bscope, exec_flops=6 * flops, detail="dgrad-x3" + shape), "x3_conv2d_same dgrad")
-                if not fused:
-                    _lib.check(_timed("conv_halo_x3_kernel", 0.0, lambda: lib.dwc_conv2d_bwd_data_ring(
-                        g.data_ptr(), w_dg(), w_dg_t(), dx.data_ptr(), B, H, W, Cx, cop, KH, KW, pad, ws.data_ptr(), nws, st),
-                        scope_name=ctx.bscope, detail="dgrad-ring" + shape), "conv2d_bwd_data_ring")
-                g_res = None                                   # consumed by the kernel's epilogue
+                    return dx, True
+                # (one arena: the interior's half sums -- small launches, contraction split -- are dead when the ring strips start)
+                ws = _sp_same(lib, g, w, owner, "dgrad", None, g_res, dx, B, H, W, Cx, cop, KH, 0, 0, flops, shape, " dgrad", at_least=nws,
+                              scope_name=ctx.bscope)
             elif half and HALO and RING_FUSED and lib.dwc_bf16_conv2d_bwd_data_same_fused_ok(B, H, W, Cx, cop, KH):
                 # interior AND border ring in one launch: the border tiles of the halo kernel fold the ring in as extra MFMAs (r06)
                 _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_bwd_data_same_fused(
                     g.data_ptr(), w_dg(), _p(g_res), dx.data_ptr(), B, H, W, Cx, cop, KH, st),
-                    scope_name=ctx.bscope, detail="dgrad-halo B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)),
-                    "conv2d_bwd_data_same_fused")
-                g_res = None                                   # consumed by the kernel's epilogue
+                    scope_name=ctx.bscope, detail="dgrad-halo" + shape), "conv2d_bwd_data_same_fused")
+                return dx, True
             elif half and HALO and lib.dwc_bf16_conv2d_same_halo_ok(B, H, W, cop, Cx, KH):
                 # interior on the halo-tiled kernel (zero rule, dgrad weights), the ring stays on the strip GEMMs
                 ws = workspace(nws, dev)
-
-                shape = " B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)
-                _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_same_halo_add(
-                    g.data_ptr(), w_dg(), None, _p(g_res), dx.data_ptr(), B, H, W, cop, Cx, KH, 0, 0, st),
-                    scope_name=ctx.bscope, detail="dgrad-halo" + shape), "conv2d_same_halo dgrad")
-                _lib.check(_timed("conv_gemm_kernel", 0.0, lambda: lib.dwc_bf16_conv2d_bwd_data_ring(
-                    g.data_ptr(), w_dg(), w_dg_t(), dx.data_ptr(), B, H, W, Cx, cop, KH, KW, pad, ws.data_ptr(), nws, st),
-                    scope_name=ctx.bscope, detail="dgrad-ring" + shape), "conv2d_bwd_data_ring")
-                g_res = None                                   # consumed by the kernel's epilogue
+                _halo_same_bf16(lib, g, w, owner, "dgrad", None, g_res, dx, B, H, W, Cx, cop, KH, 0, 0, flops, "dgrad-halo" + shape, " dgrad",
+                                ctx.bscope)
             else:
                 ws = workspace(nws, dev)
-                _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data_same", x)(
+                _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data_same", g)(
                     g.data_ptr(), w_dg(), w_dg_t(), dx.data_ptr(), B, H, W, Cx, cop, KH, KW, pad, ws.data_ptr(),
-                    ws.numel(), st), scope_name=ctx.bscope, detail="dgrad B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)),
-                    "conv2d_bwd_data_same")
-        elif (ctx.needs_input_grad[0] and (not zero) and S2DGRAD and stride == 2 and KH == 4 and KW == 4 and pad == 1
-              and 4 * B * (H // 32) * (W // 32) * (Cx // 64) >= S2DGRAD_MIN_WGS
-              and ((half and HALO and lib.dwc_bf16_conv2d_s2_halo_bwd_data_ok(B, H, W, Cx, cop))
-                   or ((not half) and X3 and lib.dwc_x3_conv2d_s2_bwd_data_ok(B, H, W, Cx, cop)))):
+                    ws.numel(), st), scope_name=ctx.bscope, detail="dgrad" + shape), "conv2d_bwd_data_same")
+                return dx, False
+            _lib.check(_timed("conv_gemm_kernel" if half else "conv_halo_x3_kernel", 0.0, lambda: _fn(lib, "conv2d_bwd_data_ring", g)(
+                g.data_ptr(), w_dg(), w_dg_t(), dx.data_ptr(), B, H, W, Cx, cop, KH, KW, pad, ws.data_ptr(), nws, st),
+                scope_name=ctx.bscope, detail="dgrad-ring" + shape), "conv2d_bwd_data_ring")
+            return dx, True                                    # (g_res: added in the interior launch's epilogue)
+        if _s2_dgrad_halo_ok(lib, half, B, H, W, Cx, cop, KH, KW, stride, pad):
             # stride-2 4x4 layers: the interior (all H x W pixels of dx) as four output-parity classes of 2x2-tap halo convolutions
             # over dY, then the border ring of the padded image as eight thin GEMM strips + band fold (reflect-pad adjoint)
             fused = bool(RING_FUSED and (half or h2_fits(g)))
             # (the fused fp32 form reads neither the im2col data-gradient layout nor the padded scratch image)
             w_dg = _prepped(w, "dgrad", cop, Cx, 2, owner, half) if half or not fused else None
-            dx = empty_cl(B, Cx, H, W, dev, dt)
-            flops = 2.0 * rows * Cout * Cin * KH * KW
-            dxp = None if fused else workspace(B * (H + 2) * (W + 2) * Cx * (2 if half else 4), dev)
-            shape = " B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)
             if half and fused:     # interior + border ring in one launch (r06: conv_halo16_bf16.inc RING, S2 == 2)
                 _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_s2_halo_bwd_data_fused(
                     g.data_ptr(), w_dg.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, st), scope_name=ctx.bscope,
                     detail="dgrad-s2halo" + shape), "conv2d_s2_halo_bwd_data_fused")
-            elif half:
-                _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_s2_halo_bwd_data(
-                    g.data_ptr(), w_dg.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, st), scope_name=ctx.bscope,
-                    detail="dgrad-s2halo" + shape), "conv2d_s2_halo_bwd_data")
-                _lib.check(_timed("conv_gemm_kernel", 0.0, lambda: lib.dwc_bf16_conv2d_bwd_data_s2_ring(
+            elif fused:            # interior + border ring in one launch (r06: pre-summed patch rows / columns, conv_halo_x3_kernel RING)
+                w_h2 = _prepped(w, "h2_dgrad", cop, Cx, 1, owner)
+                ga = amax_of(g)
+                _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_s2_bwd_data_fused(
+                    g.data_ptr(), ga[0], ga[1], w_h2.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, Cx, st), scope_name=ctx.bscope,
+                    exec_flops=3 * flops, detail="dgrad-h2s2" + shape), "h2_conv2d_s2_bwd_data_fused")
+            else:
+                dxp = workspace(B * (H + 2) * (W + 2) * Cx * (2 if half else 4), dev)
+                _s2_dgrad_halo(lib, g, w, owner, dx, B, H, W, Cx, cop, flops, ctx.bscope, shape)
+                _lib.check(_timed("conv_gemm_kernel" if half else "conv_halo_x3_kernel", 0.0, lambda: _fn(lib, "conv2d_bwd_data_s2_ring", g)(
                     g.data_ptr(), w_dg.data_ptr(), dxp.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, st), scope_name=ctx.bscope,
                     detail="dgrad-ring" + shape), "conv2d_bwd_data_s2_ring")
-            else:
-                if fused:          # interior + border ring in one launch (r06: pre-summed patch rows / columns, conv_halo_x3_kernel RING)
-                    w_h2 = _prepped(w, "h2_dgrad", cop, Cx, 1, owner)
-                    ga = amax_of(g)
-                    _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_s2_bwd_data_fused(
-                        g.data_ptr(), ga[0], ga[1], w_h2.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, Cx, st), scope_name=ctx.bscope,
-                        exec_flops=3 * flops, detail="dgrad-h2s2" + shape), "h2_conv2d_s2_bwd_data_fused")
-                elif h2_fits(g):
-                    w_h2 = _prepped(w, "h2_dgrad", cop, Cx, 1, owner)
-                    ga = amax_of(g)
-                    _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_s2_bwd_data(
-                        g.data_ptr(), ga[0], ga[1], w_h2.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, Cx, st), scope_name=ctx.bscope,
-                        exec_flops=3 * flops, detail="dgrad-h2s2" + shape), "h2_conv2d_s2_bwd_data")
-                else:
-                    w_x3 = _prepped(w, "x3_dgrad", cop, Cx, 1, owner)
-                    _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_s2_bwd_data(
-                        g.data_ptr(), w_x3.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, Cx, st), scope_name=ctx.bscope,
-                        exec_flops=6 * flops, detail="dgrad-x3s2" + shape), "x3_conv2d_s2_bwd_data")
-                if not fused:
-                    _lib.check(_timed("conv_halo_x3_kernel", 0.0, lambda: lib.dwc_conv2d_bwd_data_s2_ring(
-                        g.data_ptr(), w_dg.data_ptr(), dxp.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, st), scope_name=ctx.bscope,
-                        detail="dgrad-ring" + shape), "conv2d_bwd_data_s2_ring")
-        elif ctx.needs_input_grad[0]:
-            w_dg = _prepped(w, "dgrad", cop, Cx, stride, owner, half)
-            dx = empty_cl(B, Cx, H, W, dev, dt)
-            flops = 2.0 * rows * Cout * Cin * KH * KW
-            # scratch arena: [gradient of the padded image (folded back below)] [split-K partials]
-            esz = 2 if half else 4
-            # (zero rule: one arena [padded gradient image][split-K partials], sized by the crop entry itself)
-            pad_bytes = 0 if pad == 0 or zero else (B * (H + 2 * pad) * (W + 2 * pad) * Cx * esz + 255) // 256 * 256
-            nws = _fn(lib, "conv2d_bwd_data_crop_ws_bytes" if zero else "conv2d_bwd_data_ws_bytes", x)(B, H, W, Cx, cop, KH, KW, stride, pad)
-            base = workspace(pad_bytes + nws, dev).data_ptr() if pad_bytes + nws else 0
-            target = dx.data_ptr() if pad == 0 else base
-            wsp = base + pad_bytes if nws else None
-            if zero:
-                # the adjoint of zero padding is a crop: the scatter writes the interior of the padded gradient image into dx
-                _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data_crop", x)(
-                    g.data_ptr(), w_dg.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, KH, KW, stride, pad, wsp, nws, st),
-                    scope_name=ctx.bscope, detail="dgrad B%d %dx%d %d>%d k%d s%d zeropad" % (B, H, W, Cx, cop, KH, stride)),
-                    "conv2d_bwd_data_crop")
-            elif pad > 0 and DGRAD_FOLD and min(H, W) >= 2 * pad + 2 and Cx % (8 if half else 4) == 0:
-                # GEMM + reflect-pad adjoint in one call: interior straight into dx, only the border ring through the padded scratch
-                _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data_fold", x)(
-                    g.data_ptr(), w_dg.data_ptr(), target, dx.data_ptr(), B, H, W, Cx, cop, KH, KW, stride, pad, wsp, nws, st),
-                    scope_name=ctx.bscope, detail="dgrad B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)), "conv2d_bwd_data_fold")
-            else:
-                _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data", x)(
-                    g.data_ptr(), w_dg.data_ptr(), target, B, H, W, Cx, cop, KH, KW, stride, pad, wsp, nws, st),
-                    scope_name=ctx.bscope, detail="dgrad B%d %dx%d %d>%d k%d s%d" % (B, H, W, Cx, cop, KH, stride)), "conv2d_bwd_data")
-                if pad > 0:
-                    _lib.check(_fn(lib, "reflect_pad_adjoint", x)(target, dx.data_ptr(), B, H, W, Cx, pad, st), "reflect_pad_adjoint")
-        if g_res is not None and dx is not None:               # no fused form on this path: the plain sum
-            dx = dx + g_res.to(dx.dtype)
-        return dx, dw, db, None, None, None, None, None, None, None, None
+            return dx, False
+        _im2col_dgrad_reflect(lib, g, w, owner, dx, B, H, W, Cx, cop, KH, KW, stride, pad, flops, ctx.bscope, "dgrad" + shape)
+        return dx, False
 
     @staticmethod
-    def _zero_dgrad_halo(ctx, lib, g, g_res, w, same):
-        """Data gradient under the zero rule on the halo kernels: the zero-rule correlation of dY with the rotated filter on the image
-        grid -- what the reflect branches launch for the INTERIOR is the whole gradient.  Same families by the same size rules:
-        stride-1 halo (the residual-gradient add in its epilogue), stride-2 halo parity classes.  Returns (dx, whether g_res was
-        added); (None, False) where no halo kernel takes the shape: the caller runs the im2col GEMM with Scatter::crop."""
+    def _dgrad_zero(ctx, lib, g, g_res, w, same, flops, shape):
+        """Data gradient under the zero rule: (dx, whether g_res was added in a kernel's epilogue).  The adjoint of zero padding is a
+        crop, so on the halo kernels the zero-rule correlation of dY with the rotated filter on the image grid -- what _dgrad_reflect
+        launches for the INTERIOR -- is the whole gradient: same families by the same size rules, no ring, strips or fold.  Where no
+        halo kernel takes the shape: the im2col GEMM with Scatter::crop."""
         B, H, W, Cx, cop, KH, KW, stride, pad, act, Cin, Cout, has_b = ctx.geom
         owner = ctx.owner
         dt = g.dtype
         half = dt == BF16
-        dev, st = g.device, _stream()
-        flops = 2.0 * g.shape[0] * g.shape[2] * g.shape[3] * Cout * Cin * KH * KW
-        shape = " B%d %dx%d %d>%d k%d s%d zeropad" % (B, H, W, Cx, cop, KH, stride)
+        dev = g.device
+        dx = empty_cl(B, Cx, H, W, dev, dt)
         if same and (not half) and _x3_use(lib, B, H, W, cop, Cx, KH, KW, stride, pad, free=True):
-            dx = empty_cl(B, Cx, H, W, dev, dt)
-            ws, ks_n, ks_t = _x3_ksplit(lib, dev, B, H, W, cop, Cx, KH, 1)
-            if h2_fits(g):
-                w_h2 = _prepped(w, "h2_dgrad", cop, Cx, 1, owner)
-                ga = amax_of(g)
-                _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_same_add_ws(
-                    g.data_ptr(), ga[0], ga[1], w_h2.data_ptr(), None, _p(g_res), dx.data_ptr(), None, 0, B, H, W, cop, Cx, Cx, KH, 0, 0,
-                    _p(ws), ks_n, ks_t, st), scope_name=ctx.bscope, exec_flops=3 * flops, detail="dgrad-h2" + shape),
-                    "h2_conv2d_same zeropad dgrad")
-            else:
-                w_x3 = _prepped(w, "x3_dgrad", cop, Cx, 1, owner)
-                _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_same_add_ws(
-                    g.data_ptr(), w_x3.data_ptr(), None, _p(g_res), dx.data_ptr(), B, H, W, cop, Cx, Cx, KH, 0, 0, _p(ws), ks_n,
-                    ks_t, st), scope_name=ctx.bscope, exec_flops=6 * flops, detail="dgrad-x3" + shape), "x3_conv2d_same zeropad dgrad")
+            _sp_same(lib, g, w, owner, "dgrad", None, g_res, dx, B, H, W, Cx, cop, KH, 0, 0, flops, shape + " zeropad", " zeropad dgrad",
+                     scope_name=ctx.bscope)
             return dx, True
         if same and half and HALO and lib.dwc_bf16_conv2d_same_halo_ok(B, H, W, cop, Cx, KH):
-            dx = empty_cl(B, Cx, H, W, dev, dt)
-            w_dg = _prepped(w, "dgrad", cop, Cx, 1, owner, True)
-            _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_same_halo_add(
-                g.data_ptr(), w_dg.data_ptr(), None, _p(g_res), dx.data_ptr(), B, H, W, cop, Cx, KH, 0, 0, st),
-                scope_name=ctx.bscope, detail="dgrad-halo" + shape), "conv2d_same_halo zeropad dgrad")
+            _halo_same_bf16(lib, g, w, owner, "dgrad", None, g_res, dx, B, H, W, Cx, cop, KH, 0, 0, flops, "dgrad-halo" + shape + " zeropad",
+                            " zeropad dgrad", ctx.bscope)
             return dx, True
-        if (S2DGRAD and stride == 2 and KH == 4 and KW == 4 and pad == 1
-                and 4 * B * (H // 32) * (W // 32) * (Cx // 64) >= S2DGRAD_MIN_WGS
-                and ((half and HALO and lib.dwc_bf16_conv2d_s2_halo_bwd_data_ok(B, H, W, Cx, cop))
-                     or ((not half) and X3 and lib.dwc_x3_conv2d_s2_bwd_data_ok(B, H, W, Cx, cop)))):
-            # the four output-parity classes of 2x2-tap halo convolutions over dY write every pixel of dx: no ring under the zero rule
-            dx = empty_cl(B, Cx, H, W, dev, dt)
-            if half:
-                w_dg = _prepped(w, "dgrad", cop, Cx, 2, owner, True)
-                _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_s2_halo_bwd_data(
-                    g.data_ptr(), w_dg.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, st), scope_name=ctx.bscope,
-                    detail="dgrad-s2halo" + shape), "conv2d_s2_halo_bwd_data zeropad")
-            elif h2_fits(g):
-                w_h2 = _prepped(w, "h2_dgrad", cop, Cx, 1, owner)
-                ga = amax_of(g)
-                _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_s2_bwd_data(
-                    g.data_ptr(), ga[0], ga[1], w_h2.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, Cx, st), scope_name=ctx.bscope,
-                    exec_flops=3 * flops, detail="dgrad-h2s2" + shape), "h2_conv2d_s2_bwd_data zeropad")
-            else:
-                w_x3 = _prepped(w, "x3_dgrad", cop, Cx, 1, owner)
-                _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_s2_bwd_data(
-                    g.data_ptr(), w_x3.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, Cx, st), scope_name=ctx.bscope,
-                    exec_flops=6 * flops, detail="dgrad-x3s2" + shape), "x3_conv2d_s2_bwd_data zeropad")
+        if _s2_dgrad_halo_ok(lib, half, B, H, W, Cx, cop, KH, KW, stride, pad):
+            # the four output-parity classes write every pixel of dx: no ring under the zero rule
+            _s2_dgrad_halo(lib, g, w, owner, dx, B, H, W, Cx, cop, flops, ctx.bscope, shape + " zeropad", " zeropad")
             return dx, False
-        return None, False
+        # the scatter writes the interior of the padded gradient image into dx (one arena [padded gradient image][split-K partials],
+        # sized by the crop entry itself)
+        w_dg = _prepped(w, "dgrad", cop, Cx, stride, owner, half)
+        nws = _fn(lib, "conv2d_bwd_data_crop_ws_bytes", g)(B, H, W, Cx, cop, KH, KW, stride, pad)
+        wsp = _splitk_ws(nws, dev)
+        st = _stream()
+        _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data_crop", g)(
+            g.data_ptr(), w_dg.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, KH, KW, stride, pad, wsp, nws, st),
+            scope_name=ctx.bscope, detail="dgrad" + shape + " zeropad"), "conv2d_bwd_data_crop")
+        return dx, False
 
 
 _PAD_MODES = ("reflect", "zero")
@@ -1312,25 +1344,23 @@ class _HeadsConvWide(torch.autograd.Function):
         y = empty_cl(B, P, H, W, x.device, x.dtype)
         st = _stream()
         flops = 2.0 * B * H * W * 4 * C * KH * KW
+        shape = " B%d %dx%d %d>%d k%d" % (B, H, W, C, P, KH)
         if half and NARROW and lib.dwc_bf16_conv2d_narrow_ok(B, H, W, C, H, W // px, KH, KW + px - 1):
             # patch staged once per 16x32-pixel block, taps dealt to the waves (csrc/conv_narrow_bf16.hip)
             _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_narrow(
                 x.data_ptr(), _prepped(w4, "heads_narrow", 32, C, 1, owner, True).data_ptr(), bias.data_ptr(), y.data_ptr(), B, H, W,
-                C, H, W // px, KH, KW + px - 1, -pad, -pad, ACT["heads8"], 1, st),
-                detail="fwd-heads-narrow B%d %dx%d %d>%d k%d" % (B, H, W, C, P, KH)), "conv2d_narrow")
+                C, H, W // px, KH, KW + px - 1, -pad, -pad, ACT["heads8"], 1, st), detail="fwd-heads-narrow" + shape), "conv2d_narrow")
         elif ((not half) and X3 and NARROW_X3 and P == 4
               and lib.dwc_x3_conv2d_narrow_ok(B, H, W, C, H, W // px, KH, KW + px - 1)):
             # fp32: the same form as split products (csrc/conv_narrow_x3.hip): patch split once per 16-channel slab, taps dealt to the waves
             w_frag = _prepped(w4, "heads_narrow_x3", 32, C, 1, owner)
             _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_narrow(
                 x.data_ptr(), w_frag.data_ptr(), bias.data_ptr(), y.data_ptr(), B, H, W, C, H, W // px, KH, KW + px - 1, -pad, -pad,
-                ACT["heads"], 1, st), detail="fwd-heads-nx3 B%d %dx%d %d>%d k%d" % (B, H, W, C, P, KH), exec_flops=6 * flops),
-                "x3_conv2d_narrow")
+                ACT["heads"], 1, st), detail="fwd-heads-nx3" + shape, exec_flops=6 * flops), "x3_conv2d_narrow")
         else:
             _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_fwd_ex", x)(
                 x.data_ptr(), w_prep.data_ptr(), bias.data_ptr(), y.data_ptr(), B, H, W, C, 32, KH, KW + px - 1, 1, px, pad, pad,
-                ACT["heads8" if P == 8 else "heads"], st), detail="fwd-heads B%d %dx%d %d>%d k%d" % (B, H, W, C, P, KH)),
-                "conv2d_fwd_ex")
+                ACT["heads8" if P == 8 else "heads"], st), detail="fwd-heads" + shape), "conv2d_fwd_ex")
         ctx.save_for_backward(x, w4, y)
         ctx.owner = owner
         ctx.bscope = ("bwd:" + SCOPE) if SCOPE else ""
@@ -1347,81 +1377,52 @@ class _HeadsConvWide(torch.autograd.Function):
         pad = KH // 2
         dev = x.device
         st = _stream()
-        dy = cl(dy)
-        rows = B * H * W
-        g = empty_cl(B, P, H, W, dev, x.dtype)
-        db = torch.empty(P, dtype=torch.float32, device=dev)
-        ws = workspace(lib.dwc_act_bwd_bias_ws_bytes(rows, P), dev)
-        _lib.check(_fn(lib, "act_bwd_bias", x)(dy.data_ptr(), y.data_ptr(), g.data_ptr(), db.data_ptr(), rows, P,
-                                               ACT["heads8" if P == 8 else "heads"], ws.data_ptr(), ws.numel(), st), "act_bwd_bias")
+        g, db = _act_bwd(lib, cl(dy), y, B, P, H, W, ACT["heads8" if P == 8 else "heads"], True)
         dx = dw = None
-        flops = 2.0 * rows * 4 * C * KH * KW
-        if (ctx.needs_input_grad[0] and half and NARROW and STEM and P == 8 and C == 64 and KH == 7 and KW == 7
+        flops = 2.0 * B * H * W * 4 * C * KH * KW
+        shape = " B%d %dx%d %d>%d k%d" % (B, H, W, C, P, KH)
+        if ctx.needs_input_grad[0]:
+            dx = empty_cl(B, C, H, W, dev, x.dtype)
+        if (ctx.needs_input_grad[0] and _stem_bf16(half, P, C, KH, KW, 1, pad)
                 and lib.dwc_bf16_conv2d_stem_ok(B, H, W, H + 2 * pad, W + 2 * pad, KH, 0)):
             # data gradient = 7x7 convolution of the 8-plane gradient image with the rotated filter on the padded grid (zero
             # rule), folded by the reflect adjoint: the stem kernel of csrc/conv_narrow_bf16.hip
             w_st = _prepped(w4, "stem_steps_dgrad", 64, P, 1, ctx.owner, True)
-            dx = empty_cl(B, C, H, W, dev, x.dtype)
             base = workspace(B * (H + 2 * pad) * (W + 2 * pad) * C * 2, dev).data_ptr()
             if DGRAD_FOLD and min(H, W) >= 2 * pad + 2:
                 # interior of the padded gradient image straight into dx, only its border ring through the scratch image + band fold
                 _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_stem_crop(
                     g.data_ptr(), w_st.data_ptr(), None, base, dx.data_ptr(), pad, B, H, W, H + 2 * pad, W + 2 * pad, KH, -(KH - 1), 0, 0,
-                    st), scope_name=ctx.bscope, detail="dgrad-heads-stem B%d %dx%d %d>%d k%d" % (B, H, W, C, P, KH)), "conv2d_stem dgrad")
+                    st), scope_name=ctx.bscope, detail="dgrad-heads-stem" + shape), "conv2d_stem dgrad")
                 _lib.check(lib.dwc_bf16_reflect_pad_adjoint_band(base, dx.data_ptr(), B, H, W, C, pad, st), "reflect_pad_adjoint_band")
             else:
                 _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_stem(
                     g.data_ptr(), w_st.data_ptr(), None, base, B, H, W, H + 2 * pad, W + 2 * pad, KH, -(KH - 1), 0, 0, st),
-                    scope_name=ctx.bscope, detail="dgrad-heads-stem B%d %dx%d %d>%d k%d" % (B, H, W, C, P, KH)), "conv2d_stem dgrad")
+                    scope_name=ctx.bscope, detail="dgrad-heads-stem" + shape), "conv2d_stem dgrad")
                 _lib.check(lib.dwc_bf16_reflect_pad_adjoint(base, dx.data_ptr(), B, H, W, C, pad, st), "reflect_pad_adjoint")
-        elif (ctx.needs_input_grad[0] and (not half) and X3 and NARROW_X3 and P == 4 and C == 64 and KH == 7 and KW == 7
+        elif (ctx.needs_input_grad[0] and NARROW_X3 and _stem_x3(half, P, C, KH, KW, 1, pad)
               and DGRAD_FOLD and min(H, W) >= 2 * pad + 2 and lib.dwc_x3_conv2d_stem_ok(B, H, W, H + 2 * pad, W + 2 * pad, KH, 0)):
             # fp32: the same as split products (conv_stem_x3_kernel): interior of the padded gradient image straight into dx, its
             # border ring through the scratch image + band fold
             w_st = _prepped(w4, "stem_steps_dgrad_x3", 64, P, 1, ctx.owner)
-            dx = empty_cl(B, C, H, W, dev, x.dtype)
             base = workspace(B * (H + 2 * pad) * (W + 2 * pad) * C * 4, dev).data_ptr()
             _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_stem_crop(
                 g.data_ptr(), w_st.data_ptr(), None, base, dx.data_ptr(), pad, B, H, W, H + 2 * pad, W + 2 * pad, KH, -(KH - 1), 0, 0,
-                st), scope_name=ctx.bscope, exec_flops=6 * flops, detail="dgrad-heads-stem-x3 B%d %dx%d %d>%d k%d" % (B, H, W, C, P, KH)),
-                "x3_conv2d_stem dgrad")
+                st), scope_name=ctx.bscope, exec_flops=6 * flops, detail="dgrad-heads-stem-x3" + shape), "x3_conv2d_stem dgrad")
             _lib.check(lib.dwc_reflect_pad_adjoint_band(base, dx.data_ptr(), B, H, W, C, pad, st), "reflect_pad_adjoint_band")
         elif ctx.needs_input_grad[0]:        # data gradient: the ordinary P-channel formulation (N = C columns)
-            w_dg = _prepped(w4, "dgrad", P, C, 1, ctx.owner, half)
-            dx = empty_cl(B, C, H, W, dev, x.dtype)
-            pad_bytes = (B * (H + 2 * pad) * (W + 2 * pad) * C * (2 if half else 4) + 255) // 256 * 256
-            nws = _fn(lib, "conv2d_bwd_data_ws_bytes", x)(B, H, W, C, P, KH, KW, 1, pad)
-            base = workspace(pad_bytes + nws, dev).data_ptr()
-            if DGRAD_FOLD and min(H, W) >= 2 * pad + 2 and C % (8 if half else 4) == 0:
-                _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data_fold", x)(
-                    g.data_ptr(), w_dg.data_ptr(), base, dx.data_ptr(), B, H, W, C, P, KH, KW, 1, pad, (base + pad_bytes) if nws else None,
-                    nws, st), scope_name=ctx.bscope, detail="dgrad-heads B%d %dx%d %d>%d k%d" % (B, H, W, C, P, KH)), "conv2d_bwd_data_fold")
-            else:
-                _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data", x)(
-                    g.data_ptr(), w_dg.data_ptr(), base, B, H, W, C, P, KH, KW, 1, pad, (base + pad_bytes) if nws else None, nws,
-                    st), scope_name=ctx.bscope, detail="dgrad-heads B%d %dx%d %d>%d k%d" % (B, H, W, C, P, KH)), "conv2d_bwd_data")
-                _lib.check(_fn(lib, "reflect_pad_adjoint", x)(base, dx.data_ptr(), B, H, W, C, pad, st), "reflect_pad_adjoint")
-        if ctx.needs_input_grad[1] and half and NARROW and STEM and P == 8 and C == 64 and KH == 7 and KW == 7:
+            _im2col_dgrad_reflect(lib, g, w4, ctx.owner, dx, B, H, W, C, P, KH, KW, 1, pad, flops, ctx.bscope, "dgrad-heads" + shape)
+        if ctx.needs_input_grad[1] and (_stem_bf16(half, P, C, KH, KW, 1, pad) or (SMALLK_X3 and _stem_x3(half, P, C, KH, KW, 1, pad))):
+            # the stem's kernel with the roles swapped (A = the gradient image, Bt = x on the padded grid)
             dw = torch.empty((P, C, KH, KW), dtype=torch.float32, device=dev)
-            ws = workspace(lib.dwc_bf16_conv7_smallk_wgrad_ws_bytes(B, H, W, 1), dev)
-            _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: lib.dwc_bf16_conv7_smallk_wgrad(
-                g.data_ptr(), x.data_ptr(), dw.data_ptr(), B, H, W, P, 1, ws.data_ptr(), ws.numel(), st), scope_name=ctx.bscope,
-                detail="wgrad-heads-small B%d %dx%d %d>%d k%d" % (B, H, W, C, P, KH)), "conv7_smallk_wgrad")
-        elif ctx.needs_input_grad[1] and (not half) and X3 and SMALLK_X3 and P == 4 and C == 64 and KH == 7 and KW == 7:
-            # fp32 image heads: the same kernel with the roles swapped (A = the gradient image, Bt = x on the padded grid)
-            dw = torch.empty((P, C, KH, KW), dtype=torch.float32, device=dev)
-            ws = workspace(lib.dwc_x3_conv7_smallk_wgrad_ws_bytes(B, H, W, 1), dev)
-            _lib.check(_timed("wgrad_x3_kernel+reduce", flops, lambda: lib.dwc_x3_conv7_smallk_wgrad(
-                g.data_ptr(), x.data_ptr(), dw.data_ptr(), B, H, W, P, 1, ws.data_ptr(), ws.numel(), st), scope_name=ctx.bscope,
-                detail="wgrad-heads-small-x3 B%d %dx%d %d>%d k%d" % (B, H, W, C, P, KH), exec_flops=6 * flops), "x3_conv7_smallk_wgrad")
+            _smallk_wgrad(lib, x, g, dw, B, H, W, P, True, flops, ctx.bscope, "wgrad-heads-small", shape)
         elif ctx.needs_input_grad[1]:        # weight gradient of the wide filter bank, folded back onto the real taps
             dwide = torch.empty((32, C, KH, KW + px - 1), dtype=torch.float32, device=dev)
             nws = _fn(lib, "conv2d_bwd_weight_ex_ws_bytes", x)(B, H, W, C, 32, KH, KW + px - 1, 1, px, pad, pad)
             ws = workspace(nws, dev)
             _lib.check(_timed("conv_wgrad_kernel+reduce", flops, lambda: _fn(lib, "conv2d_bwd_weight_ex", x)(
                 x.data_ptr(), g.data_ptr(), dwide.data_ptr(), B, H, W, C, 32, KH, KW + px - 1, 1, px, pad, pad, C, 32,
-                ws.data_ptr(), ws.numel(), st), scope_name=ctx.bscope,
-                detail="wgrad-heads B%d %dx%d %d>%d k%d" % (B, H, W, C, P, KH)), "conv2d_bwd_weight_ex")
+                ws.data_ptr(), ws.numel(), st), scope_name=ctx.bscope, detail="wgrad-heads" + shape), "conv2d_bwd_weight_ex")
             # fold the px shifted copies back onto the real taps: the diagonal view (stride along p = the bank's plus one tap), one sum
             dw = dwide.as_strided((px, P, C, KH, KW), (dwide.stride(0) * P + 1,) + tuple(dwide.stride())).sum(0)
         return dx, dw, (db if ctx.needs_input_grad[2] else None), None
@@ -1440,7 +1441,9 @@ def conv2d_heads(x, w4, b4, owner=None, pad_mode="reflect"):
 
 class _Conv2dZeroPad(torch.autograd.Function):
     """relu?(conv(zero_pad(x)) + b) with FROZEN weights (the VGG16 of the perceptual loss, reference
-    networks.py:639-688): forward and data gradient only."""
+    networks.py:639-688): forward and data gradient only.  Built from the launchers of _Conv2d's zero rule, a node of its own for what
+    frozen weights allow: x is not saved, the activation backward takes no absmax slot, the im2col fallback of the data gradient works on
+    the image grid without a padded scratch image (conv2d_bwd_data_zeropad), and its spans keep their own kinds (fwd-zeropad, ...)."""
 
     @staticmethod
     def forward(ctx, x, w, b, pad, act):
@@ -1458,39 +1461,22 @@ class _Conv2dZeroPad(torch.autograd.Function):
         # fp32: the split-product halo kernel with the zero rule where the shape allows (r05; rounds 1-4 ran Winograd F(2x2,3x3) here)
         sp = bool((not half) and _x3_use(lib, B, H, W, Cx, cop, KH, KW, 1, pad, free=True))
         halo = bool(half and HALO and KH == KW and 2 * pad == KH - 1 and lib.dwc_bf16_conv2d_same_halo_ok(B, H, W, Cx, cop, KH))
-        w_prep = None if sp else _prepped(w, "fwd", cop, Cx, 1, None, half)
-        bias = None
-        if b is not None:
-            bias = b.detach() if cop == Cout else torch.nn.functional.pad(b.detach(), (0, cop - Cout))
+        bias = _padded_bias(b, Cout, cop)
         y = empty_cl(B, cop, H, W, x.device, x.dtype)
-        st = _stream()
         flops = 2.0 * B * H * W * Cout * Cin * KH * KW
-        if sp and h2_fits(x):
-            w_h2 = _prepped(w, "h2_fwd", cop, Cx, 1)
-            ks_ws, ks_n, ks_t = _x3_ksplit(lib, x.device, B, H, W, Cx, cop, KH, 1)
-            xa = amax_of(x)
-            ya, yep = out_amax(y)
-            _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_same_add_ws(
-                x.data_ptr(), xa[0], xa[1], w_h2.data_ptr(), _p(bias), None, y.data_ptr(), ya, yep, B, H, W, Cx, cop, cop, KH, act, 0,
-                _p(ks_ws), ks_n, ks_t, st), detail="fwd-h2 B%d %dx%d %d>%d k%d zeropad" % (B, H, W, Cx, cop, KH), exec_flops=3 * flops),
-                "h2_conv2d_same zeropad")
-            set_amax(y, ya, yep)
-        elif sp:
-            w_x3 = _prepped(w, "x3_fwd", cop, Cx, 1)
-            ks_ws, ks_n, ks_t = _x3_ksplit(lib, x.device, B, H, W, Cx, cop, KH, 1)
-            _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_same_add_ws(
-                x.data_ptr(), w_x3.data_ptr(), _p(bias), None, y.data_ptr(), B, H, W, Cx, cop, cop, KH, act, 0, _p(ks_ws), ks_n, ks_t, st),
-                detail="fwd-x3 B%d %dx%d %d>%d k%d zeropad" % (B, H, W, Cx, cop, KH), exec_flops=6 * flops), "x3_conv2d_same zeropad")
-        elif halo:               # bf16: the halo-tiled kernel with the zero rule
-            _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_same_halo(
-                x.data_ptr(), w_prep.data_ptr(), _p(bias), y.data_ptr(), B, H, W, Cx, cop, KH, act, 0, st),
-                detail="fwd-zeropad-halo B%d %dx%d %d>%d k%d" % (B, H, W, Cx, cop, KH)), "conv2d_same_halo zeropad")
+        shape = " B%d %dx%d %d>%d k%d" % (B, H, W, Cx, cop, KH)
+        if sp:
+            _sp_same(lib, x, w, None, "fwd", bias, None, y, B, H, W, Cx, cop, KH, act, 0, flops, shape + " zeropad", " zeropad", slot=True)
+        elif halo:
+            _halo_same_bf16(lib, x, w, None, "fwd", bias, None, y, B, H, W, Cx, cop, KH, act, 0, flops, "fwd-zeropad-halo" + shape, " zeropad")
         else:
+            w_prep = _prepped(w, "fwd", cop, Cx, 1, None, half)
+            st = _stream()
             nws = _fn(lib, "conv2d_fwd_ws_bytes", x)(B, H, W, Cx, cop, KH, KW, 1, pad)
-            wsp = workspace(nws, x.device).data_ptr() if nws else None
+            wsp = _splitk_ws(nws, x.device)
             _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_fwd_zeropad", x)(
                 x.data_ptr(), w_prep.data_ptr(), _p(bias), y.data_ptr(), B, H, W, Cx, cop, KH, KW, 1, pad, act, wsp, nws, st),
-                detail="fwd-zeropad B%d %dx%d %d>%d k%d" % (B, H, W, Cx, cop, KH)), "conv2d_fwd_zeropad")
+                detail="fwd-zeropad" + shape), "conv2d_fwd_zeropad")
         ctx.save_for_backward(w, y if act != 0 else None)
         ctx.geom = (B, H, W, Cx, cop, KH, KW, pad, act, Cin, Cout)
         return y
@@ -1502,44 +1488,27 @@ class _Conv2dZeroPad(torch.autograd.Function):
         B, H, W, Cx, cop, KH, KW, pad, act, Cin, Cout = ctx.geom
         if not ctx.needs_input_grad[0]:
             return None, None, None, None, None
-        dy = cl(dy)
+        g = dy = cl(dy)
         half = dy.dtype == BF16
-        dev, st, rows = dy.device, _stream(), B * H * W
-        g = dy
         if act != 0:
-            g = empty_cl(B, cop, H, W, dev, dy.dtype)
-            ws = workspace(lib.dwc_act_bwd_bias_ws_bytes(rows, cop), dev)
-            _lib.check(_fn(lib, "act_bwd_bias", dy)(dy.data_ptr(), y.data_ptr(), g.data_ptr(), None, rows, cop, act, ws.data_ptr(),
-                                                    ws.numel(), st), "act_bwd_bias")
-        dx = empty_cl(B, Cx, H, W, dev, dy.dtype)
-        flops = 2.0 * rows * Cout * Cin * KH * KW
+            g, _ = _act_bwd(lib, dy, y, B, cop, H, W, act, False)
+        dx = empty_cl(B, Cx, H, W, dy.device, dy.dtype)
+        flops = 2.0 * B * H * W * Cout * Cin * KH * KW
+        shape = " B%d %dx%d %d>%d k%d" % (B, H, W, Cx, cop, KH)
+        # the adjoint of zero padding is a crop: the zero-rule convolution of dY with the rotated filter, no ring at all
         if (not half) and _x3_use(lib, B, H, W, cop, Cx, KH, KW, 1, pad, free=True):
-            # the adjoint of zero padding is a crop: the zero-rule convolution of dY with the rotated filter, no ring at all
-            ws, ks_n, ks_t = _x3_ksplit(lib, dev, B, H, W, cop, Cx, KH, 1)
-            if h2_fits(g):
-                w_h2 = _prepped(w, "h2_dgrad", cop, Cx, 1)
-                ga = amax_of(g)
-                _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_h2_conv2d_same_add_ws(
-                    g.data_ptr(), ga[0], ga[1], w_h2.data_ptr(), None, None, dx.data_ptr(), None, 0, B, H, W, cop, Cx, Cx, KH, 0, 0, _p(ws),
-                    ks_n, ks_t, st), detail="dgrad-h2 B%d %dx%d %d>%d k%d zeropad" % (B, H, W, Cx, cop, KH), exec_flops=3 * flops),
-                    "h2_conv2d_same zeropad dgrad")
-            else:
-                w_x3 = _prepped(w, "x3_dgrad", cop, Cx, 1)
-                _lib.check(_timed("conv_halo_x3_kernel", flops, lambda: lib.dwc_x3_conv2d_same_add_ws(
-                    g.data_ptr(), w_x3.data_ptr(), None, None, dx.data_ptr(), B, H, W, cop, Cx, Cx, KH, 0, 0, _p(ws), ks_n, ks_t, st),
-                    detail="dgrad-x3 B%d %dx%d %d>%d k%d zeropad" % (B, H, W, Cx, cop, KH), exec_flops=6 * flops), "x3_conv2d_same zeropad dgrad")
-            return dx, None, None, None, None
-        w_dg = _prepped(w, "dgrad", cop, Cx, 1, None, half)
-        if half and HALO and KH == KW and 2 * pad == KH - 1 and lib.dwc_bf16_conv2d_same_halo_ok(B, H, W, cop, Cx, KH):
-            _lib.check(_timed("conv_gemm_kernel", flops, lambda: lib.dwc_bf16_conv2d_same_halo(
-                g.data_ptr(), w_dg.data_ptr(), None, dx.data_ptr(), B, H, W, cop, Cx, KH, 0, 0, st),
-                detail="dgrad-zeropad-halo B%d %dx%d %d>%d k%d" % (B, H, W, Cx, cop, KH)), "conv2d_same_halo zeropad dgrad")
-            return dx, None, None, None, None
-        nws = _fn(lib, "conv2d_bwd_data_zeropad_ws_bytes", dy)(B, H, W, Cx, cop, KH, KW, pad)
-        wsp = workspace(nws, dev).data_ptr() if nws else None
-        _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data_zeropad", dy)(
-            g.data_ptr(), w_dg.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, KH, KW, pad, wsp, nws, st),
-            detail="dgrad-zeropad B%d %dx%d %d>%d k%d" % (B, H, W, Cx, cop, KH)), "conv2d_bwd_data_zeropad")
+            _sp_same(lib, g, w, None, "dgrad", None, None, dx, B, H, W, Cx, cop, KH, 0, 0, flops, shape + " zeropad", " zeropad dgrad")
+        elif half and HALO and KH == KW and 2 * pad == KH - 1 and lib.dwc_bf16_conv2d_same_halo_ok(B, H, W, cop, Cx, KH):
+            _halo_same_bf16(lib, g, w, None, "dgrad", None, None, dx, B, H, W, Cx, cop, KH, 0, 0, flops, "dgrad-zeropad-halo" + shape,
+                            " zeropad dgrad")
+        else:
+            w_dg = _prepped(w, "dgrad", cop, Cx, 1, None, half)
+            st = _stream()
+            nws = _fn(lib, "conv2d_bwd_data_zeropad_ws_bytes", dy)(B, H, W, Cx, cop, KH, KW, pad)
+            wsp = _splitk_ws(nws, dy.device)
+            _lib.check(_timed("conv_gemm_kernel", flops, lambda: _fn(lib, "conv2d_bwd_data_zeropad", dy)(
+                g.data_ptr(), w_dg.data_ptr(), dx.data_ptr(), B, H, W, Cx, cop, KH, KW, pad, wsp, nws, st),
+                detail="dgrad-zeropad" + shape), "conv2d_bwd_data_zeropad")
         return dx, None, None, None, None
 
 
