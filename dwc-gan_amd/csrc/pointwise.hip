@@ -490,6 +490,23 @@ __global__ void l1_bwd_kernel(const T* __restrict__ a, const T* __restrict__ b, 
 //   out = sum_s  w_src[s] * mean_s((src - target[s])^2)  +  w_cls[s] * mean_s(BCEwithLogits(cls, labels))
 // in ONE single-workgroup launch (a few thousand elements) instead of ~25 stock elementwise / reduction launches per scale
 // and direction.  Sums are taken in a fixed order (bitwise reproducible).  labels: [B][ncls], shared by the segments.
+//
+// GAN selects the src term (DWC_GAN_*; the attribute term is the same for all three).  DWC_GAN_LSGAN is the expression above.
+// DWC_GAN_WGAN: -+ mean_s(src), minus where target[s] is 1.  DWC_GAN_NSGAN: the reference's binary_cross_entropy(sigmoid(src), all0 | all1)
+// AS WRITTEN THERE, not the stable softplus -- p = 1 / (1 + expf(-x)) and torch's clamp of the logarithm at -100, so a saturated
+// sigmoid (p rounded to 0 or 1) costs exactly 100 or 0 and carries no gradient, as it does in the reference.
+template <int GAN>
+__device__ __forceinline__ float adv_src_term(float x, float target) {
+    static_assert(GAN == DWC_GAN_WGAN || GAN == DWC_GAN_NSGAN, "the LSGAN loop is written out in the kernel");
+    if constexpr (GAN == DWC_GAN_WGAN) {
+        return x;                                                              // (the sign is applied to the segment's sum)
+    } else {
+        const float p = 1.f / (1.f + expf(-x));
+        return -fmaxf(target != 0.f ? logf(p) : log1pf(-p), -100.f);
+    }
+}
+
+template <int GAN>
 __global__ __launch_bounds__(256) void adv_tail_fwd_kernel(const float* __restrict__ src, const float* __restrict__ cls,
                                                            const float* __restrict__ labels, float* __restrict__ out, int segs, int B,
                                                            int sps, int ncls, dwc_adv_spec sp) {
@@ -499,9 +516,13 @@ __global__ __launch_bounds__(256) void adv_tail_fwd_kernel(const float* __restri
         float a = 0.f, c = 0.f;
         if (sp.w_src[s] != 0.f) {
             const float* p = src + (size_t)s * B * sps;
-            for (int i = threadIdx.x; i < B * sps; i += 256) {
-                const float d = p[i] - sp.target[s];
-                a += d * d;
+            if constexpr (GAN == DWC_GAN_LSGAN) {
+                for (int i = threadIdx.x; i < B * sps; i += 256) {
+                    const float d = p[i] - sp.target[s];
+                    a += d * d;
+                }
+            } else {
+                for (int i = threadIdx.x; i < B * sps; i += 256) a += adv_src_term<GAN>(p[i], sp.target[s]);
             }
         }
         if (sp.w_cls[s] != 0.f) {
@@ -513,11 +534,13 @@ __global__ __launch_bounds__(256) void adv_tail_fwd_kernel(const float* __restri
         }
         a = dwc_block_sum_256(a, sm);
         c = dwc_block_sum_256(c, sm);
+        if (GAN == DWC_GAN_WGAN && sp.target[s] != 0.f) a = -a;
         total += sp.w_src[s] * (a / (float)(B * sps)) + sp.w_cls[s] * (c / (float)(B * ncls));
     }
     if (threadIdx.x == 0) out[0] = total;
 }
 
+template <int GAN>
 __global__ __launch_bounds__(256) void adv_tail_bwd_kernel(const float* __restrict__ src, const float* __restrict__ cls,
                                                            const float* __restrict__ labels, const float* __restrict__ dout,
                                                            float* __restrict__ dsrc, float* __restrict__ dcls, int segs, int B, int sps,
@@ -527,7 +550,15 @@ __global__ __launch_bounds__(256) void adv_tail_bwd_kernel(const float* __restri
     for (int i = blockIdx.x * 256 + threadIdx.x; i < nsrc + ncl; i += gridDim.x * 256) {
         if (i < nsrc) {
             const int s = i / (B * sps);
-            dsrc[i] = g * sp.w_src[s] * 2.f * (src[i] - sp.target[s]) / (float)(B * sps);
+            if constexpr (GAN == DWC_GAN_LSGAN) {
+                dsrc[i] = g * sp.w_src[s] * 2.f * (src[i] - sp.target[s]) / (float)(B * sps);
+            } else if constexpr (GAN == DWC_GAN_WGAN) {
+                dsrc[i] = (sp.target[s] != 0.f ? -g : g) * sp.w_src[s] / (float)(B * sps);
+            } else {
+                // autograd of binary_cross_entropy (denominator clamped at 1e-12) through sigmoid's own backward, p (1 - p)
+                const float p = 1.f / (1.f + expf(-src[i])), q = (1.f - p) * p;
+                dsrc[i] = g * sp.w_src[s] / (float)(B * sps) * (p - (sp.target[s] != 0.f ? 1.f : 0.f)) / fmaxf(q, 1e-12f) * q;
+            }
         } else {
             const int j = i - nsrc, s = j / (B * ncls), r = j - s * (B * ncls);
             const float v = cls[j];
@@ -861,8 +892,8 @@ int dwc_gmm_kl_sp_bwd(const float* mu, const float* lv, const float* centre, int
 int dwc_adv_tail_fwd(const float* src, const float* cls, const float* labels, float* out, int segs, int B, int src_per_sample, int ncls,
                      dwc_adv_spec spec, void* stream) {
     if (!src || !cls || !labels || !out || segs < 1 || segs > 4 || B <= 0 || src_per_sample <= 0 || ncls <= 0) return DWC_EINVAL;
-    hipLaunchKernelGGL(adv_tail_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, src, cls, labels, out, segs, B, src_per_sample,
-                       ncls, spec);
+    hipLaunchKernelGGL(adv_tail_fwd_kernel<DWC_GAN_LSGAN>, dim3(1), dim3(256), 0, (hipStream_t)stream, src, cls, labels, out, segs, B,
+                       src_per_sample, ncls, spec);
     DWC_LAUNCH_CHECK();
     return DWC_OK;
 }
@@ -871,8 +902,39 @@ int dwc_adv_tail_bwd(const float* src, const float* cls, const float* labels, co
     if (!src || !cls || !labels || !dout || !dsrc || !dcls || segs < 1 || segs > 4 || B <= 0 || src_per_sample <= 0 || ncls <= 0)
         return DWC_EINVAL;
     const int n = segs * B * (src_per_sample + ncls);
-    hipLaunchKernelGGL(adv_tail_bwd_kernel, dim3((n + 255) / 256 < 64 ? (n + 255) / 256 : 64), dim3(256), 0, (hipStream_t)stream, src, cls,
-                       labels, dout, dsrc, dcls, segs, B, src_per_sample, ncls, spec);
+    hipLaunchKernelGGL(adv_tail_bwd_kernel<DWC_GAN_LSGAN>, dim3((n + 255) / 256 < 64 ? (n + 255) / 256 : 64), dim3(256), 0,
+                       (hipStream_t)stream, src, cls, labels, dout, dsrc, dcls, segs, B, src_per_sample, ncls, spec);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+int dwc_adv_tail_gan_fwd(const float* src, const float* cls, const float* labels, float* out, int segs, int B, int src_per_sample,
+                         int ncls, dwc_adv_spec spec, int gan_type, void* stream) {
+    if (gan_type != DWC_GAN_LSGAN && gan_type != DWC_GAN_NSGAN && gan_type != DWC_GAN_WGAN) return DWC_EINVAL;
+    if (gan_type == DWC_GAN_LSGAN) return dwc_adv_tail_fwd(src, cls, labels, out, segs, B, src_per_sample, ncls, spec, stream);
+    if (!src || !cls || !labels || !out || segs < 1 || segs > 4 || B <= 0 || src_per_sample <= 0 || ncls <= 0) return DWC_EINVAL;
+    if (gan_type == DWC_GAN_NSGAN)
+        hipLaunchKernelGGL(adv_tail_fwd_kernel<DWC_GAN_NSGAN>, dim3(1), dim3(256), 0, (hipStream_t)stream, src, cls, labels, out, segs, B,
+                           src_per_sample, ncls, spec);
+    else
+        hipLaunchKernelGGL(adv_tail_fwd_kernel<DWC_GAN_WGAN>, dim3(1), dim3(256), 0, (hipStream_t)stream, src, cls, labels, out, segs, B,
+                           src_per_sample, ncls, spec);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+int dwc_adv_tail_gan_bwd(const float* src, const float* cls, const float* labels, const float* dout, float* dsrc, float* dcls, int segs,
+                         int B, int src_per_sample, int ncls, dwc_adv_spec spec, int gan_type, void* stream) {
+    if (gan_type != DWC_GAN_LSGAN && gan_type != DWC_GAN_NSGAN && gan_type != DWC_GAN_WGAN) return DWC_EINVAL;
+    if (gan_type == DWC_GAN_LSGAN) return dwc_adv_tail_bwd(src, cls, labels, dout, dsrc, dcls, segs, B, src_per_sample, ncls, spec, stream);
+    if (!src || !cls || !labels || !dout || !dsrc || !dcls || segs < 1 || segs > 4 || B <= 0 || src_per_sample <= 0 || ncls <= 0)
+        return DWC_EINVAL;
+    const int n = segs * B * (src_per_sample + ncls);
+    const dim3 grid((n + 255) / 256 < 64 ? (n + 255) / 256 : 64);
+    if (gan_type == DWC_GAN_NSGAN)
+        hipLaunchKernelGGL(adv_tail_bwd_kernel<DWC_GAN_NSGAN>, grid, dim3(256), 0, (hipStream_t)stream, src, cls, labels, dout, dsrc, dcls,
+                           segs, B, src_per_sample, ncls, spec);
+    else
+        hipLaunchKernelGGL(adv_tail_bwd_kernel<DWC_GAN_WGAN>, grid, dim3(256), 0, (hipStream_t)stream, src, cls, labels, dout, dsrc, dcls,
+                           segs, B, src_per_sample, ncls, spec);
     DWC_LAUNCH_CHECK();
     return DWC_OK;
 }

@@ -128,6 +128,8 @@ SIGNATURES = {
     "dwc_lstm_seq_bwd": (c_int, [c_fp] * 7 + [c_int] * 4 + [c_fp, c_sz, c_fp, c_int, c_fp]),
     "dwc_adv_tail_fwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, AdvSpec, c_fp]),
     "dwc_adv_tail_bwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, AdvSpec, c_fp]),
+    "dwc_adv_tail_gan_fwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, AdvSpec, c_int, c_fp]),
+    "dwc_adv_tail_gan_bwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, AdvSpec, c_int, c_fp]),
     "dwc_bf16_conv2d_s2_halo_ok": (c_int, [c_int] * 5),
     "dwc_bf16_conv2d_s2_halo": (c_int, [c_fp] * 4 + [c_int] * 6 + [c_fp]),
     "dwc_x3_conv2d_same_ok": (c_int, [c_int] * 6),

@@ -608,6 +608,10 @@ RING_FUSED = int(os.environ.get("DWC_RING_FUSED", "1"))   # stride-1 data gradie
 # discriminator allows it (MsImageDis.penalty_hip_ok); 0: always torch's double backward (MsImageDis.forward_src_scale0_torch).
 # Opt-in: neither form has been timed at the c1 / c2 shapes yet (benchmarks/penalty_overhead.py).
 PENALTY_HIP = int(os.environ.get("DWC_PENALTY_HIP", "0"))
+# dis.gan_type nsgan / wgan on the one-launch loss tails (adv_tail, dwc_adv_tail_gan_*).  0: they take the term-by-term torch algebra of
+# MsImageDis.dis_loss_terms / gen_loss_terms, as before the tails took them -- the A/B partner of benchmarks/gan_tail_overhead.py.
+# lsgan is on the tail either way.
+ADV_TAIL_GAN = int(os.environ.get("DWC_ADV_TAIL_GAN", "1"))
 S2DGRAD_MIN_WGS = 192        # below this many workgroups (4 classes x blocks x 64-channel tiles) the im2col GEMM keeps the layer
 
 
@@ -2286,10 +2290,11 @@ def gmm_kl_sp(mu, lv, centre, sigma):
 # --------------------------------------------------------------------------------------
 class _AdvTail(torch.autograd.Function):
     """Adversarial loss of ONE discriminator scale over a batched pass (reference networks.py:116-170), one launch each way:
-    sum_s w_src[s] * mean_s((src - target[s])^2) + w_cls[s] * mean_s(bce_with_logits(cls, labels))."""
+    sum_s w_src[s] * mean_s((src - target[s])^2) + w_cls[s] * mean_s(bce_with_logits(cls, labels)).  ``gan`` (GAN_TYPES) swaps the src
+    term: nsgan mean_s(binary_cross_entropy(sigmoid(src), target[s])), wgan -+ mean_s(src); 0, lsgan, is the launch it always was."""
 
     @staticmethod
-    def forward(ctx, src, cls, labels, B, targets, w_src, w_cls):
+    def forward(ctx, src, cls, labels, B, targets, w_src, w_cls, gan=0):
         _require_device(src)
         lib = _lib.load()
         src, cls, labels = src.float().contiguous(), cls.float().contiguous(), labels.float().contiguous()
@@ -2303,25 +2308,41 @@ class _AdvTail(torch.autograd.Function):
         for s in range(segs):
             spec.target[s], spec.w_src[s], spec.w_cls[s] = float(targets[s]), float(w_src[s]), float(w_cls[s])
         out = torch.empty((), dtype=torch.float32, device=src.device)
-        _lib.check(lib.dwc_adv_tail_fwd(src.data_ptr(), cls.data_ptr(), labels.data_ptr(), out.data_ptr(), segs, B, sps, ncls, spec,
-                                        _stream()), "adv_tail_fwd")
+        if gan == 0:
+            _lib.check(lib.dwc_adv_tail_fwd(src.data_ptr(), cls.data_ptr(), labels.data_ptr(), out.data_ptr(), segs, B, sps, ncls, spec,
+                                            _stream()), "adv_tail_fwd")
+        else:
+            _lib.check(lib.dwc_adv_tail_gan_fwd(src.data_ptr(), cls.data_ptr(), labels.data_ptr(), out.data_ptr(), segs, B, sps, ncls,
+                                                spec, gan, _stream()), "adv_tail_gan_fwd")
         ctx.save_for_backward(src, cls, labels)
-        ctx.geom = (segs, B, sps, ncls, spec)
+        ctx.geom = (segs, B, sps, ncls, spec, gan)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         lib = _lib.load()
         src, cls, labels = ctx.saved_tensors
-        segs, B, sps, ncls, spec = ctx.geom
+        segs, B, sps, ncls, spec, gan = ctx.geom
         dsrc, dcls = torch.empty_like(src), torch.empty_like(cls)
-        _lib.check(lib.dwc_adv_tail_bwd(src.data_ptr(), cls.data_ptr(), labels.data_ptr(), dout.float().contiguous().data_ptr(),
-                                        dsrc.data_ptr(), dcls.data_ptr(), segs, B, sps, ncls, spec, _stream()), "adv_tail_bwd")
-        return dsrc, dcls, None, None, None, None, None
+        dout = dout.float().contiguous()
+        if gan == 0:
+            _lib.check(lib.dwc_adv_tail_bwd(src.data_ptr(), cls.data_ptr(), labels.data_ptr(), dout.data_ptr(), dsrc.data_ptr(),
+                                            dcls.data_ptr(), segs, B, sps, ncls, spec, _stream()), "adv_tail_bwd")
+        else:
+            _lib.check(lib.dwc_adv_tail_gan_bwd(src.data_ptr(), cls.data_ptr(), labels.data_ptr(), dout.data_ptr(), dsrc.data_ptr(),
+                                                dcls.data_ptr(), segs, B, sps, ncls, spec, gan, _stream()), "adv_tail_gan_bwd")
+        return dsrc, dcls, None, None, None, None, None, None
 
 
-def adv_tail(src, cls, labels, B, targets, w_src, w_cls):
-    return _AdvTail.apply(src, cls, labels, int(B), tuple(targets), tuple(w_src), tuple(w_cls))
+GAN_TYPES = {"lsgan": 0, "nsgan": 1, "wgan": 2}          # DWC_GAN_LSGAN / _NSGAN / _WGAN
+
+
+def adv_tail(src, cls, labels, B, targets, w_src, w_cls, gan_type="lsgan"):
+    """targets[s]: 1 = segment s is scored as real, 0 = as fake.  nsgan is the reference's binary_cross_entropy(sigmoid(src), .) as
+    written there: once the sigmoid has rounded to 0 or 1 the element costs exactly 100 (or 0) and has no gradient."""
+    if gan_type not in GAN_TYPES:
+        raise ValueError("adv_tail: gan_type must be one of %s, not %r" % (sorted(GAN_TYPES), gan_type))
+    return _AdvTail.apply(src, cls, labels, int(B), tuple(targets), tuple(w_src), tuple(w_cls), GAN_TYPES[gan_type])
 
 
 class _WeightedSum(torch.autograd.Function):

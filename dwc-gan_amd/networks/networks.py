@@ -555,17 +555,25 @@ class MsImageDis(nn.Module):
                 p.append([s, c])
         return parts
 
+    def adv_tail_ok(self):
+        """Whether adv_loss takes this discriminator's objective (else: dis_loss_terms / gen_loss_terms)."""
+        return self.dataset in ("CelebA", "CUB200") and (
+            self.gan_type == "lsgan" or (bool(ops.ADV_TAIL_GAN) and self.gan_type in ops.GAN_TYPES))
+
     def adv_loss(self, outputs, B, labels, targets, w_src, w_cls):
         """Adversarial objective of a BATCHED pass (segments of B samples: [x_fake | x_fake1 | x_real] in the D step --
         [x_fake | x_real | x_fake1 | x_real] with spectral norm --, [x_fake | x_fake1] in the G step), one tail launch per scale (hipdwc.ops.adv_tail) instead of the reference's term-by-term
         LSGAN / BCE algebra (networks.py:116-170):  sum over scales and segments s of
-        w_src[s] * mean((src_s - targets[s])^2) + w_cls[s] * BCEwithLogits(cls_s, labels).  LSGAN + CelebA/CUB200 only (the
-        shipped configuration); anything else takes the term-by-term methods below."""
-        if self.gan_type != "lsgan" or self.dataset not in ("CelebA", "CUB200"):
-            raise NotImplementedError("adv_loss covers gan_type lsgan with attribute BCE; use dis_loss_terms / gen_loss_terms")
+        w_src[s] * mean((src_s - targets[s])^2) + w_cls[s] * BCEwithLogits(cls_s, labels).  gan_type nsgan / wgan put their own src term
+        in place of the square (_gan_term with target_is_real = targets[s]; nsgan saturates as the reference does: an element whose
+        sigmoid has rounded to 0 or 1 costs exactly 100 or 0 and has no gradient).  Attribute datasets (CelebA / CUB200) only, and
+        with ops.ADV_TAIL_GAN 0 lsgan only; anything else takes the term-by-term methods below."""
+        if not self.adv_tail_ok():
+            raise NotImplementedError("adv_loss covers attribute BCE (CelebA / CUB200) with gan_type lsgan%s; use dis_loss_terms / "
+                                      "gen_loss_terms" % (", nsgan, wgan" if ops.ADV_TAIL_GAN else " (DWC_ADV_TAIL_GAN=0)"))
         loss = None
         for src, cls in outputs:
-            term = ops.adv_tail(src, cls, labels, B, targets, w_src, w_cls)
+            term = ops.adv_tail(src, cls, labels, B, targets, w_src, w_cls, gan_type=self.gan_type)
             loss = term if loss is None else loss + term
         return loss
 

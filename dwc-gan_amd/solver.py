@@ -293,7 +293,7 @@ class Solver(nn.Module):
             # in the reference (which evaluates it twice, with identical values)
             outs = self.dis(torch.cat([fakes, x4]))
             targets, w_src, w_cls, pairs = (0.0, 0.0, 1.0), (gw, gw, 2.0 * gw), (0.0, 0.0, 2.0 * cw), ((0, 2), (1, 2))
-        if self.dis.gan_type == "lsgan" and self.dis.dataset in ("CelebA", "CUB200"):
+        if self.dis.adv_tail_ok():
             # calc_dis_loss(x_fake, x_real) + calc_dis_loss(x_fake1, x_real) (reference solver.py:333-336), one tail launch per scale
             self.loss_dis = self.dis.adv_loss(outs, B, label_src, targets=targets, w_src=w_src, w_cls=w_cls)
         else:
@@ -382,7 +382,7 @@ class Solver(nn.Module):
             # one pass over [x_fake, x_fake1] (spectral norm: the reference's two calls, one iteration each; batch norm: each call's own
             # batch statistics, the running buffers stepped twice)
             outs = self.dis(x_all[B:], segments=2 if self.dis.sn_layers() or self.dis.bn_layers() else None)
-            if self.dis.gan_type == "lsgan" and self.dis.dataset in ("CelebA", "CUB200"):
+            if self.dis.adv_tail_ok():
                 self.loss_gen_adv = self.dis.adv_loss(outs, B, label_trg, targets=(1.0, 1.0), w_src=(cfg["gan_w"],) * 2,
                                                       w_cls=(cfg["cls_w"],) * 2)
             else:

@@ -348,6 +348,21 @@ int dwc_adv_tail_fwd(const float* src, const float* cls, const float* labels, fl
                      dwc_adv_spec spec, void* stream);
 int dwc_adv_tail_bwd(const float* src, const float* cls, const float* labels, const float* dout, float* dsrc, float* dcls, int segs,
                      int B, int src_per_sample, int ncls, dwc_adv_spec spec, void* stream);
+/* The same tail with the src term of any documented gan_type (reference networks.py:130-138, :157-163); the attribute term, the
+ * layouts and the launch shapes are those above, and target[s] still says whether segment s is scored as real (1) or fake (0):
+ *   DWC_GAN_LSGAN: mean((src - target)^2) -- the same kernels as above, bit for bit;
+ *   DWC_GAN_NSGAN: binary_cross_entropy(sigmoid(src), target), the reference's own composition and not the stable softplus:
+ *                  p = 1 / (1 + expf(-src)), term -max(logf(p), -100) for target 1, -max(log1pf(-p), -100) for target 0; the gradient is
+ *                  torch's for that composition, (p - t) / max(p (1 - p), 1e-12) * p (1 - p) / N: exactly 0 once p has rounded to 0 or 1;
+ *   DWC_GAN_WGAN:  -mean(src) for target 1, +mean(src) for target 0; d src is the constant -+ dout * w_src[s] / N.
+ * Any other gan_type: DWC_EINVAL, nothing launched. */
+#define DWC_GAN_LSGAN 0
+#define DWC_GAN_NSGAN 1
+#define DWC_GAN_WGAN 2
+int dwc_adv_tail_gan_fwd(const float* src, const float* cls, const float* labels, float* out, int segs, int B, int src_per_sample,
+                         int ncls, dwc_adv_spec spec, int gan_type, void* stream);
+int dwc_adv_tail_gan_bwd(const float* src, const float* cls, const float* labels, const float* dout, float* dsrc, float* dcls, int segs,
+                         int B, int src_per_sample, int ncls, dwc_adv_spec spec, int gan_type, void* stream);
 
 /* Refresh of every prepared weight layout of a network in ONE launch behind the optimiser step (SURVEY.md section 8(f) rank 1;
  * reference solver.py:240,353).  One descriptor per (OIHW master weight, prepared tensor, layout); workgroup b rebuilds
