@@ -199,7 +199,7 @@ def broadcast_module(module, src=0, group=None):
         tensors = list(module.parameters()) + list(module.buffers())
         for t in tensors:
             dist.broadcast(t.data, src=src, group=group)
-        # written through .data: bump the version counters so caches keyed on them (hipdwc.ops._prepped) notice
+        # written through .data: bump the version counters so everything kept per parameter version (hipdwc.derived) notices
         torch.autograd.graph.increment_version(tensors)
 
 

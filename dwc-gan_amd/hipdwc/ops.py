@@ -11,7 +11,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, derived
 
 ACT = {"none": 0, None: 0, "relu": 1, "lrelu": 2, "tanh": 3, "sigmoid": 4, "heads": 5, "heads8": 6}
 
@@ -79,13 +79,18 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _dev_index(dev):
+    """Index of a device, the current one's for a bare "cuda"."""
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
 _WS = {}
 
 
 def workspace(nbytes, device):
     """Scratch arena handed to the kernels (grown on demand, never shrunk): one per (device, stream) -- kernels on one
     stream run in order and may share it, concurrent streams must not."""
-    key = (device.index if device.index is not None else torch.cuda.current_device(), _stream())
+    key = (_dev_index(device), _stream())
     buf = _WS.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
@@ -234,44 +239,183 @@ def _padc(n, dtype):
 # --------------------------------------------------------------------------------------
 # weight layouts, cached per parameter version
 # --------------------------------------------------------------------------------------
-_WCACHE = {}   # id(tensor) -> (weakref to it, {layout key: (version, prepared tensor)})
+_WCACHE = derived.Cache()      # parameter -> {layout key: (stamp, prepared tensor, refresh recipe or None)}
+_X3_BANK_IDX = {}      # (kind, filter shape, pads, device) -> int32 gather table of a split filter bank (see _x3_bank_layout)
+# layout kinds of dwc_weight_refresh_multi: the DWC_REFRESH_* enum of include/dwcgan_hip.h
+REFRESH = {"FWD_F32": 0, "DGRAD_F32": 1, "FWD_BF16": 2, "DGRAD_BF16": 3, "X3_FWD": 4, "X3_DGRAD": 5, "H2_FWD": 8, "H2_DGRAD": 9}
 
 
-_X3_BANK_IDX = {}      # (kind, filter shape, pads, device) -> int32 gather table of a split filter bank (see _prepped)
+def _im2col_layout(w, kind, cout_pad, cin_pad, stride, half):
+    """fwd / dgrad / dgrad_t: the K-major rows of the im2col GEMMs, fp32 or bf16 (dwc_[bf16_]weight_prepare_fwd / _dgrad)."""
+    lib = _lib.load()
+    cout, cin, kh, kw = w.shape
+    transposed = kind == "dgrad_t"  # dgrad layout of the filter with its two spatial axes swapped (taps enumerated kw-major)
+    wc = (w.detach().transpose(2, 3) if transposed else w.detach()).contiguous()
+    dg = kind != "fwd"
+    pre = "dwc_bf16_" if half else "dwc_"
+    n = getattr(lib, pre + "weight_prepared_elems")(cout, cin, kh, kw, stride, cout_pad, cin_pad, int(dg))
+    out = torch.empty(n, dtype=BF16 if half else torch.float32, device=w.device)
+    if dg:
+        _lib.check(getattr(lib, pre + "weight_prepare_dgrad")(wc.data_ptr(), out.data_ptr(), cout, cin, kh, kw, stride,
+                                                              cout_pad, cin_pad, _stream()), "weight_prepare_dgrad")
+        rows = cin_pad if stride == 1 else 4 * cin_pad
+    else:
+        _lib.check(getattr(lib, pre + "weight_prepare_fwd")(wc.data_ptr(), out.data_ptr(), cout, cin, kh, kw, cout_pad, cin_pad,
+                                                            _stream()), "weight_prepare_fwd")
+        rows = cout_pad
+    if (transposed and kh != kw) or n % rows:
+        return out, None
+    # (Kp = the padded row length the single-layout entry point chose: n elements / rows)
+    return out, dict(kind=REFRESH[("DGRAD" if dg else "FWD") + ("_BF16" if half else "_F32")], n_items=n, Cout=cout, Cin=cin, KH=kh,
+                     KW=kw, stride=stride, cout_pad=cout_pad, cin_pad=cin_pad, Kp=n // rows, transpose_hw=int(transposed))
+
+
+def _split_layout(w, kind, cout_pad, cin_pad, stride, half):
+    """x3_fwd / x3_dgrad: three bf16 planes per (tap, 16-channel slab) [tap][slab][plane][row][16] (dwc_x3_weight_prepare).
+    h2_fwd / h2_dgrad: two f16 planes of s_w * w in that order + {s_w, 1 / s_w} (dwc_h2_weight_prepare), s_w from the filter's
+    largest magnitude (dwc_absmax: padding zeros do not change it).  rows = cout_pad forward / cin_pad for the data gradient, the
+    contraction runs over the other (zero-padded) channel count."""
+    lib = _lib.load()
+    co, ci, kh, kw = w.shape
+    exact = co == cout_pad and ci == cin_pad
+    wz = w.detach()
+    if not exact:
+        wz = torch.zeros((cout_pad, cin_pad, kh, kw), dtype=torch.float32, device=w.device)
+        wz[:co, :ci] = w.detach()
+    wz = wz.contiguous()
+    dg = kind.endswith("_dgrad")
+    rows, kdim = (cin_pad, cout_pad) if dg else (cout_pad, cin_pad)
+    if kind.startswith("h2_"):
+        # (zeros: the last 8 bytes are the filter's absmax slot of the fused refresh, which must start below every epoch)
+        out = torch.zeros(lib.dwc_h2_weight_prepared_elems(rows, kdim, kh), dtype=torch.float16, device=w.device)
+        slot, ep = amax_slot(w.device)
+        _lib.check(lib.dwc_absmax(wz.data_ptr(), wz.numel(), slot, ep, _stream()), "absmax(weight)")
+        _lib.check(lib.dwc_h2_weight_prepare(wz.data_ptr(), out.data_ptr(), cout_pad, cin_pad, kh, rows, int(dg), slot, ep, _stream()),
+                   "h2_weight_prepare")
+    else:
+        out = torch.empty(lib.dwc_x3_weight_prepared_elems(rows, kdim, kh), dtype=BF16, device=w.device)
+        _lib.check(lib.dwc_x3_weight_prepare(wz.data_ptr(), out.data_ptr(), cout_pad, cin_pad, kh, rows, int(dg), _stream()),
+                   "x3_weight_prepare")
+    if not exact:
+        return out, None
+    return out, dict(kind=REFRESH[kind.upper()], n_items=kh * kh * ((kdim + 15) // 16) * rows * 16, Cout=co, Cin=ci, KH=kh, KW=kw,
+                     rows=rows, kdim=kdim)
+
+
+def _step_bank(w, dgrad, taps, planes):
+    """fp32 7x7 filter -> [k-step][64 channels][16] with taps * planes = 8 numbers per half, tap = taps * (2j + h) + t, the halves
+    of a row swapped by (co>>3)&1: 25 steps of 2 taps x 8 planes (csrc/conv_narrow_bf16.hip conv_stem_kernel), 13 steps of
+    4 taps x 4 planes (csrc/conv_narrow_x3.hip).  w is the stem filter [64][P<=planes][7][7]; `dgrad`: the heads filter
+    [P<=planes][64][7][7], rotated and transposed (the data gradient is a convolution of the gradient image)."""
+    wf = w.detach().float()
+    if dgrad:
+        wf = wf.flip(2, 3).permute(1, 0, 2, 3)                          # [64][P][7][7]
+    co, pl, kh, kw = wf.shape
+    assert co == 64 and pl <= planes and kh == 7 and kw == 7 and taps * planes == 8
+    nst = (49 + 2 * taps - 1) // (2 * taps)
+    bank = torch.zeros((64, nst * 2 * taps, planes), dtype=torch.float32, device=w.device)     # [co][tap (49 + zeros)][plane]
+    bank[:, :49, :pl] = wf.permute(0, 2, 3, 1).reshape(64, 49, pl)
+    steps = bank.view(64, nst, 2, 8).permute(1, 0, 2, 3).contiguous()           # [j][co][h][t * planes + p]
+    swap = ((torch.arange(64, device=w.device) >> 3) & 1).bool()
+    # (torch.where, not boolean-mask indexing: a mask index is a nonzero() = a host synchronisation, six per c2 iteration -- r06)
+    return torch.where(swap.view(1, 64, 1, 1), steps.flip(2), steps).reshape(nst, 64, 16)
+
+
+def _stem_layout(w, kind, cout_pad, cin_pad, stride, half):
+    """stem_steps / stem_steps_dgrad: the bf16 step bank [25][64][16]."""
+    return _step_bank(w, kind == "stem_steps_dgrad", 1, 8).to(BF16).contiguous(), None
+
+
+def _shifted_bank(w, px):
+    """[px][*w.shape[:-1]][KW + px - 1]: copy p holds w shifted right by p taps, zeros elsewhere (the "wide" filter banks of the
+    image heads).  One fill + ONE strided copy (the diagonal view's stride along p is the bank's plus one tap) instead of px
+    pad + stack launches."""
+    kw = w.shape[-1]
+    bank = torch.zeros((px,) + tuple(w.shape[:-1]) + (kw + px - 1,), dtype=w.dtype, device=w.device)
+    diag = bank.as_strided((px,) + tuple(w.shape), (bank.stride(0) + 1,) + tuple(bank.stride()[1:]))
+    diag.copy_(w.unsqueeze(0).expand((px,) + tuple(w.shape)))
+    return bank
+
+
+def _wide_bank(w, dgrad, cout_pad, cin_pad):
+    """The P-plane heads (P = w.shape[0]: 4, or 8 on the bf16 path) as px = 32/P pixels x P planes: bank [p*P + co][ci][KH][KW+px-1],
+    copy p shifted right by p taps.  `dgrad`: px shifted copies of the flipped, transposed filter [p*P + ci][co][KH][KW+px-1]
+    (dwc_conv2d_bwd_data_image); cout_pad = gathered (dY) channels, cin_pad = P image planes (4 fp32 / 8 bf16), px = 32 / P."""
+    wf = w.detach().float()
+    if dgrad:
+        co, ci, kh, kw = w.shape
+        wf = torch.zeros((cin_pad, cout_pad, kh, kw), dtype=torch.float32, device=w.device)
+        wf[:ci, :co] = w.detach().flip(2, 3).permute(1, 0, 2, 3)
+    px = 32 // wf.shape[0]
+    return _shifted_bank(wf, px).reshape(px * wf.shape[0], wf.shape[1], wf.shape[2], wf.shape[3] + px - 1)
+
+
+def _wide_layout(w, kind, cout_pad, cin_pad, stride, half):
+    """heads_wide / dgrad_image: the wide bank as forward rows of the im2col GEMM (a derived bank: no refresh recipe)."""
+    bank = _wide_bank(w, kind == "dgrad_image", cout_pad, cin_pad)
+    return _im2col_layout(bank, "fwd", bank.shape[0], cin_pad if kind == "heads_wide" else cout_pad, 1, half)[0], None
+
+
+def _narrow_layout(base, kind, cout_pad, cin_pad, stride, half):
+    """heads_narrow / dgrad_image_narrow: `base`, the prepared wide bank ([32][taps*64] rows), in MFMA-fragment order
+    [tap][q][hi][row][8] for csrc/conv_narrow_bf16.hip."""
+    ch = cout_pad if kind == "dgrad_image_narrow" else cin_pad          # contraction channels (64)
+    taps = base.numel() // (32 * ch)
+    out = base.view(32, taps, ch // 16, 2, 8).permute(1, 2, 3, 0, 4).reshape(taps, -1)
+    return torch.nn.functional.pad(out, (0, 0, 0, (taps + 7) // 8 * 8 - taps)).contiguous(), None     # zero taps: every wave walks the same count
+
+
+_NARROW_BASE = {"heads_narrow": "heads_wide", "dgrad_image_narrow": "dgrad_image"}
 
 
 def _x3_bank_recipe(kind, w, cout_pad, cin_pad):
     """fp32 filter (or its element numbers) -> the UNSPLIT bank of csrc/conv_narrow_x3.hip in the kernels' element order.
-    stem_steps*: [13 k-steps][64 channels][(h ^ ((co>>3)&1))*8 + 4t + p] with tap = 4j + 2h + t (stem_steps_x3: w is the stem
-    filter [64][P<=4][7][7]; stem_steps_dgrad_x3: the heads filter [P<=4][64][7][7], rotated and transposed).
-    heads_narrow_x3 / dgrad_image_narrow_x3: the wide bank [32][64][7][14] (8 pixels x 4 planes, copy p = the filter shifted right
-    by p taps) as [slab q of 16 channels][tap, 98 padded to 104 with zeros][lane = half*32 + bank row][8 channels 16q + 8*half ..]."""
-    if kind in ("stem_steps_x3", "stem_steps_dgrad_x3"):
-        wf = w.float()
-        if kind == "stem_steps_dgrad_x3":
-            wf = wf.flip(2, 3).permute(1, 0, 2, 3)                      # [64][P][7][7]
-        co, pl, kh, kw = wf.shape
-        assert co == 64 and pl <= 4 and kh == 7 and kw == 7
-        bank = torch.zeros((64, 52, 4), dtype=torch.float32, device=w.device)      # [co][tap (49 + 3 zero)][plane]
-        bank[:, :49, :pl] = wf.permute(0, 2, 3, 1).reshape(64, 49, pl)
-        steps = bank.view(64, 13, 2, 8).permute(1, 0, 2, 3).contiguous()           # [j][co][h][t*4 + p]
-        swap = ((torch.arange(64, device=w.device) >> 3) & 1).bool()
-        steps[:, swap] = steps[:, swap].flip(2)
-        return steps.reshape(13, 64, 16)
-    if kind == "heads_narrow_x3":
-        px = 32 // w.shape[0]
-        bank = _shifted_bank(w.float(), px).reshape(32, w.shape[1], w.shape[2], w.shape[3] + px - 1)
-    else:
-        co, ci, kh, kw = w.shape
-        px = 32 // cin_pad
-        wf = torch.zeros((cin_pad, cout_pad, kh, kw), dtype=torch.float32, device=w.device)
-        wf[:ci, :co] = w.float().flip(2, 3).permute(1, 0, 2, 3)
-        bank = _shifted_bank(wf, px).reshape(px * cin_pad, cout_pad, kh, kw + px - 1)
+    stem_steps*: `_step_bank` [13 k-steps][64 channels][(h ^ ((co>>3)&1))*8 + 4t + p] with tap = 4j + 2h + t.
+    heads_narrow_x3 / dgrad_image_narrow_x3: the wide bank [32][64][7][14] (8 pixels x 4 planes) as
+    [slab q of 16 channels][tap, 98 padded to 104 with zeros][lane = half*32 + bank row][8 channels 16q + 8*half ..]."""
+    if kind.startswith("stem_steps"):
+        return _step_bank(w, kind == "stem_steps_dgrad_x3", 2, 4)
+    bank = _wide_bank(w, kind == "dgrad_image_narrow_x3", cout_pad, cin_pad)
     rows_, ch, kh, kww = bank.shape
     assert rows_ == 32 and ch == 64
     v = bank.permute(2, 3, 1, 0).reshape(kh * kww, 4, 2, 8, 32).permute(1, 0, 2, 4, 3)                  # [q][tap][half][row][8]
     ntp = (kh * kww + 7) // 8 * 8
     return torch.nn.functional.pad(v.reshape(4, kh * kww, 512), (0, 0, 0, ntp - kh * kww))
+
+
+def _x3_bank_layout(w, kind, cout_pad, cin_pad, stride, half):
+    """stem_steps_x3 / stem_steps_dgrad_x3 / heads_narrow_x3 / dgrad_image_narrow_x3, the split filter banks of
+    csrc/conv_narrow_x3.hip: a fixed permutation (+ zero padding) of the OIHW filter, split into three exact bf16 planes.  The
+    permutation is built ONCE per layout as an index table (`_x3_bank_recipe` applied to the element numbers); every later build is
+    one launch (dwc_x3_gather_split)."""
+    lib = _lib.load()
+    ikey = (kind, tuple(w.shape), cout_pad, cin_pad, str(w.device))
+    idx = _X3_BANK_IDX.get(ikey)
+    if idx is None:
+        num = (torch.arange(w.numel(), dtype=torch.float32, device=w.device) + 1.0).view(w.shape)      # 0 = "zero element"
+        idx = (_x3_bank_recipe(kind, num, cout_pad, cin_pad).reshape(-1).round().to(torch.int32) - 1).contiguous()
+        _X3_BANK_IDX[ikey] = idx
+    n = idx.numel()
+    src = w.detach()
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        src = src.float().contiguous()
+    out = torch.empty(3 * n, dtype=BF16, device=w.device)
+    _lib.check(lib.dwc_x3_gather_split(src.data_ptr(), idx.data_ptr(), out.data_ptr(), n, _stream()), "x3_gather_split")
+    if kind.startswith("stem_steps"):
+        assert out.numel() == lib.dwc_x3_conv2d_stem_weight_elems()             # [plane][13][64][16]
+    else:
+        # [plane][q][tap][lane][8] -> the kernel's [q][tap][plane][lane][8]
+        out = out.view(3, 4, n // (4 * 512), 512).permute(1, 2, 0, 3).contiguous().view(-1)
+        assert out.numel() == lib.dwc_x3_conv2d_narrow_weight_elems(7, 14)
+    return out, None
+
+
+# kind -> builder(w, kind, cout_pad, cin_pad, stride, half) -> (prepared tensor, descriptor fields of dwc_weight_refresh_multi or None)
+_LAYOUTS = dict(
+    [(k, _im2col_layout) for k in ("fwd", "dgrad", "dgrad_t")] + [(k, _split_layout) for k in ("x3_fwd", "x3_dgrad", "h2_fwd", "h2_dgrad")]
+    + [(k, _stem_layout) for k in ("stem_steps", "stem_steps_dgrad")] + [(k, _wide_layout) for k in ("heads_wide", "dgrad_image")]
+    + [(k, _narrow_layout) for k in _NARROW_BASE]
+    + [(k, _x3_bank_layout) for k in ("stem_steps_x3", "stem_steps_dgrad_x3", "heads_narrow_x3", "dgrad_image_narrow_x3")])
 
 
 def _prepped(w, kind, cout_pad, cin_pad, stride, owner=None, half=False):
@@ -280,162 +424,18 @@ def _prepped(w, kind, cout_pad, cin_pad, stride, owner=None, half=False):
     fresh tensor on every call (a reshaped Linear weight, the concatenated image heads): the cache then lives on the
     owner(s) and is keyed on their versions, so the derived tensor does not defeat it."""
     owners = (w,) if owner is None else (tuple(owner) if isinstance(owner, (tuple, list)) else (owner,))
-    anchor = owners[0]
-    slot = _WCACHE.get(id(anchor))
-    if slot is None or slot[0]() is not anchor:
-        wid = id(anchor)
-        slot = (weakref.ref(anchor, lambda _r, wid=wid: _WCACHE.pop(wid, None)), {})
-        _WCACHE[wid] = slot
-    ent = slot[1]
     key = (kind, cout_pad, cin_pad, stride, tuple(w.shape), bool(half))
-    # validity = (version counter, storage address) of every owner: writers that go through ``.data``
-    # (dist.broadcast(t.data), load_state_dict on a rebound tensor, Module.to()) do not always bump the version but most
-    # of them move or re-bind the storage; the in-tree ``.data`` writers bump the version explicitly
-    # (dp.broadcast_module, host.moving_average, host.weights_init)
-    stamp = tuple((o._version, o.data_ptr()) for o in owners)
-    if ent.get(key, (None, None))[0] == stamp:
-        return ent[key][1]
-    lib = _lib.load()
-    if kind in ("x3_fwd", "x3_dgrad"):
-        # three bf16 planes per (tap, 16-channel slab) [tap][slab][plane][row][16] (dwc_x3_weight_prepare); rows = cout_pad
-        # forward / cin_pad for the data gradient, the contraction runs over the other (zero-padded) channel count
-        co, ci, kh, kw = w.shape
-        wz = w.detach()
-        if co != cout_pad or ci != cin_pad:
-            wz = torch.zeros((cout_pad, cin_pad, kh, kw), dtype=torch.float32, device=w.device)
-            wz[:co, :ci] = w.detach()
-        dg = kind == "x3_dgrad"
-        rows, kdim = (cin_pad, cout_pad) if dg else (cout_pad, cin_pad)
-        out = torch.empty(lib.dwc_x3_weight_prepared_elems(rows, kdim, kh), dtype=BF16, device=w.device)
-        _lib.check(lib.dwc_x3_weight_prepare(wz.contiguous().data_ptr(), out.data_ptr(), cout_pad, cin_pad, kh, rows, int(dg),
-                                             _stream()), "x3_weight_prepare")
-        recipe = None
-        if co == cout_pad and ci == cin_pad:
-            recipe = _recipe(w, owners, kind=5 if dg else 4, n_items=kh * kh * ((kdim + 15) // 16) * rows * 16, Cout=co, Cin=ci,
-                             KH=kh, KW=kw, rows=rows, kdim=kdim)
-        ent[key] = (stamp, out, recipe)
-        return out
-    if kind in ("h2_fwd", "h2_dgrad"):
-        # two f16 planes of s_w * w per (tap, 16-channel slab) + {s_w, 1 / s_w} (dwc_h2_weight_prepare), s_w from the filter's largest
-        # magnitude (dwc_absmax: padding zeros do not change it)
-        co, ci, kh, kw = w.shape
-        wz = w.detach()
-        if co != cout_pad or ci != cin_pad:
-            wz = torch.zeros((cout_pad, cin_pad, kh, kw), dtype=torch.float32, device=w.device)
-            wz[:co, :ci] = w.detach()
-        wz = wz.contiguous()
-        dg = kind == "h2_dgrad"
-        rows, kdim = (cin_pad, cout_pad) if dg else (cout_pad, cin_pad)
-        # (zeros: the last 8 bytes are the filter's absmax slot of the fused refresh, which must start below every epoch)
-        out = torch.zeros(lib.dwc_h2_weight_prepared_elems(rows, kdim, kh), dtype=torch.float16, device=w.device)
-        slot, ep = amax_slot(w.device)
-        _lib.check(lib.dwc_absmax(wz.data_ptr(), wz.numel(), slot, ep, _stream()), "absmax(weight)")
-        _lib.check(lib.dwc_h2_weight_prepare(wz.data_ptr(), out.data_ptr(), cout_pad, cin_pad, kh, rows, int(dg), slot, ep, _stream()),
-                   "h2_weight_prepare")
-        recipe = None
-        if co == cout_pad and ci == cin_pad:
-            recipe = _recipe(w, owners, kind=9 if dg else 8, n_items=kh * kh * ((kdim + 15) // 16) * rows * 16, Cout=co, Cin=ci,
-                             KH=kh, KW=kw, rows=rows, kdim=kdim)
-        ent[key] = (stamp, out, recipe)
-        return out
-    if kind in ("stem_steps", "stem_steps_dgrad"):
-        # csrc/conv_narrow_bf16.hip conv_stem_kernel: [25 k-steps][64 channels][2 taps x 8 planes] bf16, halves of a row swapped
-        # by (co>>3)&1.  stem_steps: w is the stem filter [64][P<=8][7][7]; stem_steps_dgrad: w is the heads filter
-        # [P<=8][64][7][7], rotated and transposed (the data gradient is a convolution of the 8-plane gradient image)
-        wf = w.detach().float()
-        if kind == "stem_steps_dgrad":
-            wf = wf.flip(2, 3).permute(1, 0, 2, 3)                      # [64][P][7][7]
-        co, pl, kh, kw = wf.shape
-        assert co == 64 and pl <= 8 and kh == 7 and kw == 7
-        bank = torch.zeros((64, 50, 8), dtype=torch.float32, device=w.device)      # [co][tap (49 + 1 zero)][plane]
-        bank[:, :49, :pl] = wf.permute(0, 2, 3, 1).reshape(64, 49, pl)
-        steps = bank.view(64, 25, 2, 8).permute(1, 0, 2, 3).contiguous()           # [j][co][h][p]
-        swap = ((torch.arange(64, device=w.device) >> 3) & 1).bool()
-        # (torch.where, not boolean-mask indexing: a mask index is a nonzero() = a host synchronisation, six per c2 iteration -- r06)
-        steps = torch.where(swap.view(1, 64, 1, 1), steps.flip(2), steps)
-        out = steps.reshape(25, 64, 16).to(BF16).contiguous()
-        ent[key] = (stamp, out)
-        return out
-    if kind in ("stem_steps_x3", "stem_steps_dgrad_x3", "heads_narrow_x3", "dgrad_image_narrow_x3"):
-        # Split filter banks of csrc/conv_narrow_x3.hip: a fixed permutation (+ zero padding) of the OIHW filter, split into three
-        # exact bf16 planes.  The permutation is built ONCE per layout as an index table (the torch recipe below applied to the
-        # element numbers); every later refresh is one launch (dwc_x3_gather_split).
-        ikey = (kind, tuple(w.shape), cout_pad, cin_pad, str(w.device))
-        idx = _X3_BANK_IDX.get(ikey)
-        if idx is None:
-            num = (torch.arange(w.numel(), dtype=torch.float32, device=w.device) + 1.0).view(w.shape)      # 0 = "zero element"
-            idx = (_x3_bank_recipe(kind, num, cout_pad, cin_pad).reshape(-1).round().to(torch.int32) - 1).contiguous()
-            _X3_BANK_IDX[ikey] = idx
-        n = idx.numel()
-        src = w.detach()
-        if src.dtype != torch.float32 or not src.is_contiguous():
-            src = src.float().contiguous()
-        out = torch.empty(3 * n, dtype=BF16, device=w.device)
-        _lib.check(lib.dwc_x3_gather_split(src.data_ptr(), idx.data_ptr(), out.data_ptr(), n, _stream()), "x3_gather_split")
-        if kind.startswith("stem_steps"):
-            assert out.numel() == lib.dwc_x3_conv2d_stem_weight_elems()             # [plane][13][64][16]
-        else:
-            # [plane][q][tap][lane][8] -> the kernel's [q][tap][plane][lane][8]
-            ntp = n // (4 * 512)
-            out = out.view(3, 4, ntp, 512).permute(1, 2, 0, 3).contiguous().view(-1)
-            assert out.numel() == lib.dwc_x3_conv2d_narrow_weight_elems(7, 14)
-        ent[key] = (stamp, out)
-        return out
-    if kind in ("heads_narrow", "dgrad_image_narrow"):
-        # the wide bank ([32][taps*64] prepared rows) in MFMA-fragment order [tap][q][hi][row][8] for csrc/conv_narrow_bf16.hip
-        base = _prepped(w, "heads_wide" if kind == "heads_narrow" else "dgrad_image", cout_pad, cin_pad, stride, owner, True)
-        ch = cout_pad if kind == "dgrad_image_narrow" else cin_pad          # contraction channels (64)
-        taps = base.numel() // (32 * ch)
-        out = base.view(32, taps, ch // 16, 2, 8).permute(1, 2, 3, 0, 4).reshape(taps, -1)
-        out = torch.nn.functional.pad(out, (0, 0, 0, (taps + 7) // 8 * 8 - taps)).contiguous()      # zero taps: every wave walks the same count
-        ent[key] = (stamp, out)
-        return out
-    if kind == "heads_wide":
-        # the P-plane heads (P = w.shape[0]: 4, or 8 on the bf16 path) as px = 32/P pixels x P planes:
-        # bank [p*P + co][ci][KH][KW+px-1], copy p shifted right by p taps
-        px = 32 // w.shape[0]
-        bank = _shifted_bank(w.detach(), px).reshape(32, w.shape[1], w.shape[2], w.shape[3] + px - 1)
-        out = _prepped(bank, "fwd", 32, cin_pad, 1, half=half)
-        ent[key] = (stamp, out)
-        return out
-    if kind == "dgrad_image":
-        # bank of px shifted copies of the flipped, transposed filter: [p*P + ci][co][KH][KW+px-1] (dwc_conv2d_bwd_data_image);
-        # cout_pad = gathered (dY) channels, cin_pad = P image planes (4 fp32 / 8 bf16), px = 32 / P
-        co, ci, kh, kw = w.shape
-        px = 32 // cin_pad
-        wf = torch.zeros((cin_pad, cout_pad, kh, kw), dtype=torch.float32, device=w.device)
-        wf[:ci, :co] = w.detach().flip(2, 3).permute(1, 0, 2, 3)
-        bank = _shifted_bank(wf, px).reshape(px * cin_pad, cout_pad, kh, kw + px - 1)
-        out = _prepped(bank, "fwd", px * cin_pad, cout_pad, 1, half=half)
-        ent[key] = (stamp, out)
-        return out
-    cout, cin, kh, kw = w.shape
-    wc = w.detach().contiguous()
-    transposed = kind == "dgrad_t"
-    if transposed:                  # dgrad layout of the filter with its two spatial axes swapped (taps enumerated kw-major)
-        wc = w.detach().transpose(2, 3).contiguous()
-        kind = "dgrad"
-    pre = "dwc_bf16_" if half else "dwc_"
-    n = getattr(lib, pre + "weight_prepared_elems")(cout, cin, kh, kw, stride, cout_pad, cin_pad, int(kind == "dgrad"))
-    out = torch.empty(n, dtype=BF16 if half else torch.float32, device=w.device)
-    if kind == "fwd":
-        _lib.check(getattr(lib, pre + "weight_prepare_fwd")(wc.data_ptr(), out.data_ptr(), cout, cin, kh, kw, cout_pad, cin_pad,
-                                                            _stream()), "weight_prepare_fwd")
-        rows, kdim = cout_pad, kh * kw * cin_pad
-    else:
-        _lib.check(getattr(lib, pre + "weight_prepare_dgrad")(wc.data_ptr(), out.data_ptr(), cout, cin, kh, kw, stride,
-                                                              cout_pad, cin_pad, _stream()), "weight_prepare_dgrad")
-        rows, kdim = (cin_pad, kh * kw * cout_pad) if stride == 1 else (4 * cin_pad, 4 * cout_pad)
-    recipe = None
-    if (not transposed or kh == kw) and n % rows == 0:
-        # (Kp = the padded row length the single-layout entry point chose: n elements / rows)
-        recipe = _recipe(w, owners, kind=(2 if half else 0) + (kind == "dgrad"), n_items=n, Cout=cout, Cin=cin, KH=kh, KW=kw,
-                         stride=stride, cout_pad=cout_pad, cin_pad=cin_pad, Kp=n // rows, transpose_hw=int(transposed))
-    ent[key] = (stamp, out, recipe)
-    return out
+    ent = _WCACHE.get(owners, key)
+    if ent is not None:
+        return ent[1]
+    at = derived.stamp(owners)
+    base = _NARROW_BASE.get(kind)           # (the fragment orders are made from a layout that is cached in its own right)
+    src = w if base is None else _prepped(w, base, cout_pad, cin_pad, stride, owner, True)
+    out, fields = _LAYOUTS[kind](src, kind, cout_pad, cin_pad, stride, half)
+    return _WCACHE.put(owners, key, out, _recipe(w, owners, fields), at)
 
 
-_PCAT = {}     # id(first parameter) -> (weakref, {key: (stamp, buffer)})
+_PCAT = derived.Cache()        # first parameter -> {(stack, ids of the parameters): (stamp, buffer, None)}
 
 
 class _CatParams(torch.autograd.Function):
@@ -445,23 +445,16 @@ class _CatParams(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, stack, *ps):
-        anchor = ps[0]
-        slot = _PCAT.get(id(anchor))
-        if slot is None or slot[0]() is not anchor:
-            aid = id(anchor)
-            slot = (weakref.ref(anchor, lambda _r, aid=aid: _PCAT.pop(aid, None)), {})
-            _PCAT[aid] = slot
-        key = (bool(stack), tuple(id(p) for p in ps))
-        stamp = tuple((p._version, p.data_ptr()) for p in ps)
-        ent = slot[1].get(key)
-        if ent is None or ent[0] != stamp:
+        key = (bool(stack), tuple([id(p) for p in ps]))
+        ent = _PCAT.get(ps, key)
+        if ent is not None:
+            buf = ent[1]
+        else:
             with torch.no_grad():
-                buf = torch.stack([p.detach() for p in ps]) if stack else torch.cat([p.detach() for p in ps], 0)
-            ent = (stamp, buf)
-            slot[1][key] = ent
+                buf = _PCAT.put(ps, key, torch.stack([p.detach() for p in ps]) if stack else torch.cat([p.detach() for p in ps], 0))
         ctx.stack = bool(stack)
         ctx.sizes = [p.shape[0] for p in ps]
-        return ent[1].view_as(ent[1])
+        return buf.view_as(buf)
 
     @staticmethod
     def backward(ctx, g):
@@ -484,8 +477,8 @@ def cat_params(params, stack=False):
         return torch.stack(params) if stack else torch.cat(params, 0)
     if not (torch.is_grad_enabled() and any(p.requires_grad for p in params)):
         return _CatParams.apply(stack, *params)
-    key = (bool(stack), tuple(id(p) for p in params))
-    stamp = tuple((p._version, p.data_ptr(), p.requires_grad) for p in params)
+    key = (bool(stack), tuple([id(p) for p in params]))
+    stamp = (derived.stamp(params), [p.requires_grad for p in params])
     ent = _PCAT_LIVE.get(key)
     if ent is not None and ent[0] == stamp and all(r() is p for r, p in zip(ent[1], params)):
         return ent[2]
@@ -495,17 +488,6 @@ def cat_params(params, stack=False):
             del _PCAT_LIVE[k]
     _PCAT_LIVE[key] = (stamp, [weakref.ref(p) for p in params], out)
     return out
-
-
-def _shifted_bank(w, px):
-    """[px][*w.shape[:-1]][KW + px - 1]: copy p holds w shifted right by p taps, zeros elsewhere (the "wide" filter banks of the
-    image heads).  One fill + ONE strided copy (the diagonal view's stride along p is the bank's plus one tap) instead of px
-    pad + stack launches."""
-    kw = w.shape[-1]
-    bank = torch.zeros((px,) + tuple(w.shape[:-1]) + (kw + px - 1,), dtype=w.dtype, device=w.device)
-    diag = bank.as_strided((px,) + tuple(w.shape), (bank.stride(0) + 1,) + tuple(bank.stride()[1:]))
-    diag.copy_(w.unsqueeze(0).expand((px,) + tuple(w.shape)))
-    return bank
 
 
 _REFRESH_DT = np.dtype([("src", "<u8"), ("dst", "<u8"), ("n_items", "<u8"), ("kind", "<i4"), ("Cout", "<i4"), ("Cin", "<i4"),
@@ -518,10 +500,11 @@ REFRESH_STATS = {"launches": 0, "layouts": 0}
 _REFRESH_EPOCH = 0
 
 
-def _recipe(w, owners, **fields):
-    """Descriptor fields with which dwc_weight_refresh_multi can rebuild this layout from the owning parameter's storage, or
-    None when the layout was not built straight from it (derived banks: the fused heads, the NHWC8 stems)."""
-    if len(owners) != 1 or w.data_ptr() != owners[0].data_ptr() or not w.detach().is_contiguous() or w.dtype != torch.float32:
+def _recipe(w, owners, fields):
+    """The descriptor fields a builder returned, with which dwc_weight_refresh_multi can rebuild its layout from the owning
+    parameter's storage, or None when the layout was not built straight from it (derived banks: the fused heads, the NHWC8 stems)."""
+    if fields is None or len(owners) != 1 or w.data_ptr() != owners[0].data_ptr() or not w.detach().is_contiguous() \
+            or w.dtype != torch.float32:
         return None
     return fields
 
@@ -532,24 +515,21 @@ def refresh_prepared(params):
     recipe), stay with the lazy per-layout path of _prepped.  Returns the number of layouts rebuilt."""
     todo = []
     for p in params:
-        slot = _WCACHE.get(id(p))
-        if slot is None or slot[0]() is not p:
-            continue
-        stamp = ((p._version, p.data_ptr()),)
-        for key, val in slot[1].items():
-            if len(val) > 2 and val[2] is not None and val[0] != stamp:
-                todo.append((p, slot[1], key, val, stamp))
+        ents = _WCACHE.entries(p)
+        if ents:
+            stamp = derived.stamp((p,))
+            todo += [(p, key, val, stamp) for key, val in ents.items() if val[2] is not None and val[0] != stamp]
     if not todo:
         return 0
     lib = _lib.load()
     dev = todo[0][0].device
     # (the recipe is part of the identity: a lazily rebuilt layout may reuse the address of another layout of the same parameter)
-    ident = tuple((p.data_ptr(), val[1].data_ptr(), tuple(sorted(val[2].items()))) for p, _, _, val, _ in todo)
+    ident = tuple((p.data_ptr(), val[1].data_ptr(), tuple(sorted(val[2].items()))) for p, _, val, _ in todo)
     table = _REFRESH_TABLES.get(ident)
     if table is None:
         desc = np.zeros(len(todo), dtype=_REFRESH_DT)
         cd, cs = [], []
-        for i, (p, _, _, val, _) in enumerate(todo):
+        for i, (p, _, val, _) in enumerate(todo):
             desc[i]["src"], desc[i]["dst"] = p.data_ptr(), val[1].data_ptr()
             for k, v in val[2].items():
                 desc[i][k] = v
@@ -559,7 +539,7 @@ def refresh_prepared(params):
         host = torch.from_numpy(desc.view(np.uint8).reshape(-1)).pin_memory()
         table = (host.to(dev, non_blocking=True), torch.tensor(cd, dtype=torch.int32, device=dev),
                  torch.tensor(np.array(cs, dtype=np.uint32).view(np.int32), dtype=torch.int32, device=dev), len(cd),
-                 int(any(int(v[3][2]["kind"]) in (8, 9) for v in todo)))
+                 int(any(v[2][2]["kind"] in (REFRESH["H2_FWD"], REFRESH["H2_DGRAD"]) for v in todo)))
         if len(_REFRESH_TABLES) > 16:
             _REFRESH_TABLES.clear()
         _REFRESH_TABLES[ident] = table
@@ -567,8 +547,8 @@ def refresh_prepared(params):
     _REFRESH_EPOCH += 1          # (epoch of the filters' absmax slots this refresh raises: larger at every call)
     _lib.check(lib.dwc_weight_refresh_multi(table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(), table[3], table[4],
                                             _REFRESH_EPOCH, _stream()), "weight_refresh_multi")
-    for p, ent, key, val, stamp in todo:
-        ent[key] = (stamp, val[1], val[2])
+    for p, key, _, stamp in todo:
+        _WCACHE.restamp(p, key, stamp)
     REFRESH_STATS["launches"] += 1
     REFRESH_STATS["layouts"] += len(todo)
     return len(todo)
@@ -627,7 +607,7 @@ def amax_slot(dev):
     """A fresh (slot address, epoch) pair: slots are handed out round robin, the epoch of a slot grows by one per lap, and a slot is
     raised by atomic max on (epoch << 32 | magnitude bits) -- so nothing is ever zeroed.  A pair stays valid for AMAX_SLOTS later
     pairs (hundreds of iterations); a consumer that meets another epoch poisons its result with NaN."""
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    key = _dev_index(dev)
     pool = _AMAX.get(key)
     if pool is None:
         pool = [torch.zeros(AMAX_SLOTS, dtype=torch.int64, device=dev), 0]
@@ -646,7 +626,7 @@ def amax_live(t, c=False):
         c = getattr(t, "_dwc_amax", None)
     if c is None or c[2] != t._version or c[3] != t.data_ptr():
         return None
-    pool = _AMAX.get(t.device.index if t.device.index is not None else torch.cuda.current_device())
+    pool = _AMAX.get(_dev_index(t.device))
     if pool is None:
         return None
     index = (c[1] - 1) * AMAX_SLOTS + (c[0] - pool[0].data_ptr()) // 8
@@ -691,7 +671,7 @@ AMAX_CHECK = int(os.environ.get("DWC_AMAX_CHECK", "0"))
 
 def _amax_verify(t, c):
     """DWC_AMAX_CHECK=1 (debugging, synchronises): the slot attached to ``t`` must hold at least max|t|."""
-    pool = _AMAX[t.device.index if t.device.index is not None else torch.cuda.current_device()][0]
+    pool = _AMAX[_dev_index(t.device)][0]
     word = int(pool[(c[0] - pool.data_ptr()) // 8])
     bits = word & 0xffffffff
     if (word >> 32) != c[1]:
@@ -760,7 +740,7 @@ def _x3_ksplit(lib, dev, B, H, W, Cx, cop, K, stride, at_least=0):
     if not need:
         ws = workspace(at_least, dev) if at_least else None
         return ws, at_least, None
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), _stream())
+    key = (_dev_index(dev), _stream())
     row = _X3_TICKETS.get(key)
     if row is None:
         row = torch.zeros(int(lib.dwc_x3_conv2d_ksplit_ticket_words()), dtype=torch.int32, device=dev)
@@ -1754,7 +1734,7 @@ LSTM_SEQ_MAX_WORKGROUPS = 0  # > 0: cap on the persistent launches' grid (hipdwc
 def _lstm_status(device):
     """The sticky hand-off status word of the persistent LSTM launches on `device` (dwc_lstm_seq_*: bit 0 forward, bit 1
     backward timed out).  It is NOT in the scratch arena: no later op overwrites it."""
-    key = device.index if device.index is not None else torch.cuda.current_device()
+    key = _dev_index(device)
     ent = _LSTM_STATUS.get(key)
     if ent is None:
         ent = [torch.zeros(1, dtype=torch.int32, device=device), torch.zeros(1, dtype=torch.int32).pin_memory(), None]
@@ -1784,27 +1764,17 @@ def lstm_status_poll(device, wait=False):
         ent[2].record()
 
 
-_LSTM_DERIVED = {}     # (kind, id(first owner parameter)) -> (weakref, stamp, tensor derived from the owners' values)
-
-
-def _stamp(params):
-    """Validity stamp of values derived from `params`, as `_prepped` keys its layouts: (version counter, storage address) of each."""
-    return None if params is None else tuple((p._version, p.data_ptr()) for p in params)
+_LSTM_DERIVED = derived.Cache()        # first owner parameter -> {kind: (stamp, tensor derived from the owners' values, None)}
 
 
 def _lstm_derived(kind, owners, stamp, build):
     """`build()` -- a tensor computed from stacked LSTM parameters alone -- kept until one of `owners` (the direction parameters the
-    stack was made from) changes.  `stamp`: their `_stamp` at the time the stacked values were read, so a backward that runs after
-    an optimiser step neither finds nor leaves an entry that does not belong to its values.  Without owners: built on every call."""
+    stack was made from) changes.  `stamp`: their `derived.stamp` at the time the stacked values were read, so a backward that runs
+    after an optimiser step neither finds nor leaves an entry that does not belong to its values.  Without owners: built on every call."""
     if owners is None:
         return build()
-    key = (kind, id(owners[0]))
-    ent = _LSTM_DERIVED.get(key)
-    if ent is not None and ent[0]() is owners[0] and ent[1] == stamp:
-        return ent[2]
-    buf = build()
-    _LSTM_DERIVED[key] = (weakref.ref(owners[0], lambda _r, key=key: _LSTM_DERIVED.pop(key, None)), stamp, buf)
-    return buf
+    ent = _LSTM_DERIVED.get(owners, kind, stamp)
+    return ent[1] if ent is not None else _LSTM_DERIVED.put(owners, kind, build(), None, stamp)
 
 
 def lstm_layer_fwd(x, lens, w_ih, w_hh, b_ih, b_hh, owners=None, owners_hh=None, owners_b=None):
@@ -1820,7 +1790,7 @@ def lstm_layer_fwd(x, lens, w_ih, w_hh, b_ih, b_hh, owners=None, owners_hh=None,
     # dense products stay with torch: the stacked tensor is a cached buffer whose address may be reused)
     hip_gemm = bool(LSTM_GEMM and owners is not None and gemm_ok(I, 4 * H) and gemm_ok(H, 4 * H))
     if hip_gemm:
-        bsum = _lstm_derived("bsum", owners_b, _stamp(owners_b), lambda: b_ih.detach() + b_hh.detach())
+        bsum = _lstm_derived("bsum", owners_b, owners_b and derived.stamp(owners_b), lambda: b_ih.detach() + b_hh.detach())
         X = X.contiguous()
         xproj = torch.empty((2, T * B, 4 * H), dtype=torch.float32, device=dev)                               # [2,TB,4H]
         for d in range(2):
@@ -1844,7 +1814,7 @@ def lstm_layer_fwd(x, lens, w_ih, w_hh, b_ih, b_hh, owners=None, owners_hh=None,
         _lib.check(lib.dwc_lstm_fwd(xproj.data_ptr(), w_hh_c.data_ptr(), lens.data_ptr(), out.data_ptr(), c.data_ptr(),
                                     gates.data_ptr(), T, B, H, 2, _stream()), "lstm_fwd")
     saved = {"tensors": (X, lens, w_ih, w_hh_c, out, c, gates), "shape": (T, B, I, H), "hip_gemm": hip_gemm, "owners": owners,
-             "owners_hh": owners_hh, "hh_stamp": _stamp(owners_hh)}
+             "owners_hh": owners_hh, "hh_stamp": owners_hh and derived.stamp(owners_hh)}
     return out, c, saved
 
 
@@ -2234,19 +2204,16 @@ def l1_mean(a, b, image=False):
 
 
 GMM_FUSED = int(os.environ.get("DWC_GMM_FUSED", "1"))      # the KL style-space term on dwc_gmm_kl_sp_* (0: torch's elementwise algebra)
-_SIGMA_F = {}                                               # id(sigma tensor) -> (weakref, version, python float)
+_SIGMA_F = derived.Cache()                                   # sigma tensor -> {None: (stamp, python float, None)}
 
 
 def _scalar_value(t):
     """Python float of a 0-dim CONSTANT tensor (Solver.sigma), read from the device once per tensor and version -- not once per call,
     which would make the host wait for the stream inside every iteration."""
-    if not torch.is_tensor(t):
+    if not isinstance(t, torch.Tensor):
         return float(t)
-    ent = _SIGMA_F.get(id(t))
-    if ent is None or ent[0]() is not t or ent[1] != t._version:
-        ent = (weakref.ref(t), t._version, float(t.detach().float().item()))
-        _SIGMA_F[id(t)] = ent
-    return ent[2]
+    ent = _SIGMA_F.get((t,), None)
+    return ent[1] if ent is not None else _SIGMA_F.put((t,), None, float(t.detach().float().item()))
 
 
 class _GmmKlSp(torch.autograd.Function):
