@@ -1209,11 +1209,14 @@ __device__ __forceinline__ void bn_merge(float& cnt, float& d, float& m2, float 
 // summed in chunk order, mean offset d_n = (pivot_n - pivot_0) + s1_n / HW and M2_n = s2_n - s1_n^2 / HW about its own pivot, merged in
 // sample order), the 16 lanes are merged in lane order by lane 0: M2 = sum M2_n + HW sum (m_n - m)^2 in a fixed order, every mean
 // kept as a small offset from the segment's first pixel.  Lane 0 then steps the running buffers of its channel through `order`.
+// With `moments` (synchronised batch norm, dwc_syncbn_moments) the chain stops after the merge: lane 0 writes the segment's
+// (count, mean, M2) to moments[3][S][C] instead, for the exchange between ranks, and mean / rstd / the buffers are not touched.
 template <typename T>
 __global__ __launch_bounds__(1024) void bn_stats_final(const T* __restrict__ x, const float* __restrict__ part, float* __restrict__ mean,
                                                        float* __restrict__ rstd, float* __restrict__ running_mean,
                                                        float* __restrict__ running_var, int S, int Bs, int HW, int C, int chunks,
-                                                       size_t plane, float eps, float momentum, dwc_bn_order order) {
+                                                       size_t plane, float eps, float momentum, dwc_bn_order order,
+                                                       float* __restrict__ moments = nullptr) {
     __shared__ float sm[3][16][64];
     __shared__ float st[2][DWC_BN_MAX_SEGMENTS][64];       // mean and unbiased variance per segment (written and read by lane 0 only)
     const int cl = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -1240,6 +1243,12 @@ __global__ __launch_bounds__(1024) void bn_stats_final(const T* __restrict__ x, 
         if (g == 0 && c < C) {
             for (int k = 1; k < 16; ++k) bn_merge(cnt, d, m2, sm[0][k][cl], sm[1][k][cl], sm[2][k][cl]);
             const float mu = p0 + d;
+            if (moments) {
+                moments[(size_t)s * C + c] = cnt;
+                moments[(size_t)(S + s) * C + c] = mu;
+                moments[(size_t)(2 * S + s) * C + c] = m2;
+                continue;
+            }
             mean[(size_t)s * C + c] = mu;
             rstd[(size_t)s * C + c] = 1.f / sqrtf(m2 / cnt + eps);
             st[0][s][cl] = mu;
@@ -1265,6 +1274,42 @@ __global__ void bn_eval_stats(const float* __restrict__ running_mean, const floa
     if (c >= C) return;
     mean[c] = running_mean[c];
     rstd[c] = 1.f / sqrtf(running_var[c] + eps);
+}
+
+// Synchronised batch norm, after the all-gather: moments_all[R][3][S][C] holds every rank's (count, mean, M2) of its part of each
+// segment.  grid ceil(C / 64), 64 threads, one channel each: per segment the R entries are merged with bn_merge in RANK order, the
+// means as offsets from rank 0's -> mean, rstd and the unbiased variance of the union; the running buffers are then stepped
+// through `order` as bn_stats_final steps them.  The same input gives the same bits on every rank; R = 1 gives bn_stats_final's.
+__global__ __launch_bounds__(64) void bn_sync_final(const float* __restrict__ moments_all, int R, float* __restrict__ mean,
+                                                    float* __restrict__ rstd, float* __restrict__ running_mean,
+                                                    float* __restrict__ running_var, int S, int C, float eps, float momentum,
+                                                    dwc_bn_order order) {
+    __shared__ float st[2][DWC_BN_MAX_SEGMENTS][64];       // mean and unbiased variance per segment (each thread its own column)
+    const int cl = threadIdx.x;
+    const int c = blockIdx.x * 64 + cl;
+    if (c >= C) return;
+    const size_t sc = (size_t)S * C;
+    for (int s = 0; s < S; ++s) {
+        const float* m = moments_all + (size_t)s * C + c;
+        const float p0 = m[sc];
+        float cnt = 0.f, d = 0.f, m2 = 0.f;
+        for (int r = 0; r < R; ++r, m += 3 * sc) bn_merge(cnt, d, m2, m[0], m[sc] - p0, m[2 * sc]);
+        const float mu = p0 + d;
+        mean[(size_t)s * C + c] = mu;
+        rstd[(size_t)s * C + c] = 1.f / sqrtf(m2 / cnt + eps);
+        st[0][s][cl] = mu;
+        st[1][s][cl] = m2 / (cnt - 1.f);
+    }
+    if (running_mean) {
+        float rm = running_mean[c], rv = running_var[c];
+        for (int j = 0; j < order.n; ++j) {
+            const int s = order.idx[j];
+            rm = (1.f - momentum) * rm + momentum * st[0][s][cl];
+            rv = (1.f - momentum) * rv + momentum * st[1][s][cl];
+        }
+        running_mean[c] = rm;
+        running_var[c] = rv;
+    }
 }
 
 // y = act((x - mean[s, c]) * (rstd[s, c] * gamma[c]) + beta[c]); grid (row chunks, S * Bs), geometry of in_apply
@@ -1438,13 +1483,15 @@ __global__ __launch_bounds__(1024) void bn_bwd_final(const float* __restrict__ p
 }
 
 // dx = gamma * rstd * (g - sum g / N - xhat * sum g xhat / N), the sums of the element's segment (coupled == 0, eval mode: the
-// statistics are constants, dx = gamma * rstd * g); grid (row chunks, S * Bs)
+// statistics are constants, dx = gamma * rstd * g); grid (row chunks, S * Bs).  `sums` is [R][2][S][C]: the prologue adds the R entries
+// in order (R = 1: the launch's own sums; synchronised batch norm: every rank's, in rank order) and N = n_seg is the element count
+// of the whole segment, over all ranks.
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_apply(const T* __restrict__ dy, const T* __restrict__ x, const float* __restrict__ mean,
                                                     const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, const float* __restrict__ sums, T* __restrict__ dx,
-                                                    int S, int Bs, int HW, int C, int rows_per_chunk, int act, int coupled,
-                                                    unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
+                                                    int S, int Bs, int HW, int C, int rows_per_chunk, int act, int coupled, int R,
+                                                    float n_seg, unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
     constexpr int V = VecOf<T>::V;
     const RowGeom<V> geo(C);
     const int cq = geo.cq, groups = geo.groups, col = geo.col, rg = geo.rg;
@@ -1452,7 +1499,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const T* __restrict__ dy, co
     const int n = blockIdx.y;
     const size_t s = (size_t)(n / Bs) * C + col * V;
     const float slope = dwc_act_slope(act);
-    const float inv_n = 1.f / ((float)Bs * (float)HW);
+    const float inv_n = 1.f / n_seg;
     float mu[V], rs[V], sc[V], be[V], k1[V], k2[V];
     ldf<V>(mean, s, mu);
     ldf<V>(rstd, s, rs);
@@ -1468,6 +1515,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const T* __restrict__ dy, co
     if (coupled) {
         ldf<V>(sums, s, k1);
         ldf<V>(sums + (size_t)S * C, s, k2);
+        for (int r = 1; r < R; ++r) {
+            float a[V], b[V];
+            ldf<V>(sums + (size_t)(2 * r) * S * C, s, a);
+            ldf<V>(sums + (size_t)(2 * r + 1) * S * C, s, b);
+#pragma unroll
+            for (int k = 0; k < V; ++k) k1[k] += a[k], k2[k] += b[k];
+        }
 #pragma unroll
         for (int k = 0; k < V; ++k) k1[k] *= inv_n, k2[k] *= inv_n;
     }
@@ -1566,7 +1620,73 @@ int batchnorm_bwd_t(const T* dy, const T* x, const float* mean, const float* rst
     DWC_LAUNCH_CHECK();
     const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
     hipLaunchKernelGGL(bn_bwd_apply<T>, dim3(ra.chunks, B), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, sums, dx, S, Bs, HW, C,
-                       ra.rows_per_chunk, act, training ? 1 : 0, amax, amax_ep);
+                       ra.rows_per_chunk, act, training ? 1 : 0, 1, (float)Bs * (float)HW, amax, amax_ep);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+
+// ---- synchronised batch norm: the two chains above cut where per-(segment, channel) numbers exist, for the exchange between ranks.
+// Bs * HW == 1 is legal in every phase: the count that must reach 2 is the segment's over all ranks, which the caller knows.
+bool bn_order_ok(const dwc_bn_order& order, int S) {
+    if (order.n < 0 || order.n > DWC_BN_MAX_SEGMENTS) return false;
+    for (int j = 0; j < order.n; ++j)
+        if (order.idx[j] < 0 || order.idx[j] >= S) return false;
+    return true;
+}
+
+template <typename T>
+int syncbn_moments_t(const T* x, float* moments, int S, int Bs, int HW, int C, void* ws, size_t ws_bytes, void* stream) {
+    if (!bn_shape_ok(S, Bs, HW, C, VecOf<T>::V) || !x || !moments) return DWC_EINVAL;
+    const BatchNormScratch sc(S, Bs, HW, C);
+    if (!ws || ws_bytes < sc.bytes) return DWC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)ws;
+    hipLaunchKernelGGL(in_stats_partial<T>, dim3(sc.rs.chunks, S * Bs), dim3(256), 0, st, x, part, HW, C, sc.rs.rows_per_chunk, sc.plane);
+    DWC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_stats_final<T>, dim3((C + 63) / 64), dim3(1024), 0, st, x, part, (float*)nullptr, (float*)nullptr,
+                       (float*)nullptr, (float*)nullptr, S, Bs, HW, C, sc.rs.chunks, sc.plane, 0.f, 0.f, dwc_bn_order{}, moments);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+
+template <typename T>
+int syncbn_apply_t(const T* x, const float* mean, const float* rstd, const float* gamma, const float* beta, T* y, int S, int Bs, int HW,
+                   int C, int act, void* stream, unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
+    if (!bn_shape_ok(S, Bs, HW, C, VecOf<T>::V) || !dwc_act_is_simple_host(act) || act < 0 || !mean || !rstd) return DWC_EINVAL;
+    const int B = S * Bs;
+    const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
+    hipLaunchKernelGGL(bn_apply<T>, dim3(ra.chunks, B), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, beta, y, Bs, HW, C,
+                       ra.rows_per_chunk, act, amax, amax_ep);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+
+template <typename T>
+int syncbn_bwd_sums_t(const T* dy, const T* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* sums,
+                      float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act, void* ws, size_t ws_bytes, void* stream) {
+    if (!bn_shape_ok(S, Bs, HW, C, VecOf<T>::V) || !dwc_act_is_simple_host(act) || act < 0 || !sums) return DWC_EINVAL;
+    const BatchNormScratch sc(S, Bs, HW, C);
+    if (!ws || ws_bytes < sc.bytes) return DWC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)ws;
+    hipLaunchKernelGGL(bn_bwd_partial<T>, dim3(sc.rs.chunks, S * Bs), dim3(256), 0, st, dy, x, mean, rstd, gamma, beta, part, Bs, HW, C,
+                       sc.rs.rows_per_chunk, sc.plane, act);
+    DWC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_bwd_final, dim3((C + 63) / 64), dim3(1024), 0, st, part, sums, dgamma, dbeta, S, Bs, C, sc.rs.chunks, sc.plane);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+
+template <typename T>
+int syncbn_bwd_apply_t(const T* dy, const T* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                       const float* sums_all, int R, long n_global, T* dx, int S, int Bs, int HW, int C, int act, void* stream,
+                       unsigned long long* amax = nullptr, unsigned amax_ep = 0) {
+    if (!bn_shape_ok(S, Bs, HW, C, VecOf<T>::V) || !dwc_act_is_simple_host(act) || act < 0 || !sums_all) return DWC_EINVAL;
+    if (R < 1 || n_global < 2 || n_global < (long)Bs * HW) return DWC_EINVAL;
+    const int B = S * Bs;
+    const RowSplit ra = plan_apply(B, HW, C, VecOf<T>::V);
+    hipLaunchKernelGGL(bn_bwd_apply<T>, dim3(ra.chunks, B), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, gamma, beta, sums_all,
+                       dx, S, Bs, HW, C, ra.rows_per_chunk, act, 1, R, (float)n_global, amax, amax_ep);
     DWC_LAUNCH_CHECK();
     return DWC_OK;
 }
@@ -1614,6 +1734,66 @@ int dwc_bf16_batchnorm_bwd(const void* dy, const void* x, const float* mean, con
                            int training, void* ws, size_t ws_bytes, void* stream) {
     return batchnorm_bwd_t<dwc_bf16>((const dwc_bf16*)dy, (const dwc_bf16*)x, mean, rstd, gamma, beta, (dwc_bf16*)dx, dgamma, dbeta, S,
                                      Bs, HW, C, act, training, ws, ws_bytes, stream);
+}
+
+/* ---- synchronised batch norm: the phases between which the ranks exchange per-(segment, channel) numbers ---- */
+size_t dwc_syncbn_ws_bytes(int S, int Bs, int HW, int C) {
+    return S < 1 || Bs < 1 || HW < 1 || C < 1 ? 0 : BatchNormScratch(S, Bs, HW, C).bytes;
+}
+int dwc_syncbn_moments(const float* x, float* moments, int S, int Bs, int HW, int C, void* ws, size_t ws_bytes, void* stream) {
+    return syncbn_moments_t<float>(x, moments, S, Bs, HW, C, ws, ws_bytes, stream);
+}
+int dwc_bf16_syncbn_moments(const void* x, float* moments, int S, int Bs, int HW, int C, void* ws, size_t ws_bytes, void* stream) {
+    return syncbn_moments_t<dwc_bf16>((const dwc_bf16*)x, moments, S, Bs, HW, C, ws, ws_bytes, stream);
+}
+int dwc_syncbn_finalise(const float* moments_all, int R, float* mean, float* rstd, float* running_mean, float* running_var, int S,
+                        int C, float eps, float momentum, dwc_bn_order order, void* stream) {
+    if (R < 1 || S < 1 || S > DWC_BN_MAX_SEGMENTS || C < 1 || !moments_all || !mean || !rstd) return DWC_EINVAL;
+    if (!bn_order_ok(order, S) || (!running_mean) != (!running_var)) return DWC_EINVAL;
+    hipLaunchKernelGGL(bn_sync_final, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, moments_all, R, mean, rstd, running_mean,
+                       running_var, S, C, eps, momentum, order);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+int dwc_syncbn_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* y, int S,
+                     int Bs, int HW, int C, int act, void* stream) {
+    return syncbn_apply_t<float>(x, mean, rstd, gamma, beta, y, S, Bs, HW, C, act, stream);
+}
+int dwc_syncbn_apply_amax(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* y, int S,
+                          int Bs, int HW, int C, int act, void* out_amax, unsigned out_epoch, void* stream) {
+    return syncbn_apply_t<float>(x, mean, rstd, gamma, beta, y, S, Bs, HW, C, act, stream, (unsigned long long*)out_amax, out_epoch);
+}
+int dwc_bf16_syncbn_apply(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, void* y, int S,
+                          int Bs, int HW, int C, int act, void* stream) {
+    return syncbn_apply_t<dwc_bf16>((const dwc_bf16*)x, mean, rstd, gamma, beta, (dwc_bf16*)y, S, Bs, HW, C, act, stream);
+}
+int dwc_syncbn_bwd_sums(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                        float* sums, float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act, void* ws, size_t ws_bytes,
+                        void* stream) {
+    return syncbn_bwd_sums_t<float>(dy, x, mean, rstd, gamma, beta, sums, dgamma, dbeta, S, Bs, HW, C, act, ws, ws_bytes, stream);
+}
+int dwc_bf16_syncbn_bwd_sums(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
+                             const float* beta, float* sums, float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act,
+                             void* ws, size_t ws_bytes, void* stream) {
+    return syncbn_bwd_sums_t<dwc_bf16>((const dwc_bf16*)dy, (const dwc_bf16*)x, mean, rstd, gamma, beta, sums, dgamma, dbeta, S, Bs, HW,
+                                       C, act, ws, ws_bytes, stream);
+}
+int dwc_syncbn_bwd_apply(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                         const float* sums_all, int R, long n_global, float* dx, int S, int Bs, int HW, int C, int act,
+                         void* stream) {
+    return syncbn_bwd_apply_t<float>(dy, x, mean, rstd, gamma, beta, sums_all, R, n_global, dx, S, Bs, HW, C, act, stream);
+}
+int dwc_syncbn_bwd_apply_amax(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                              const float* beta, const float* sums_all, int R, long n_global, float* dx, int S, int Bs, int HW, int C,
+                              int act, void* out_amax, unsigned out_epoch, void* stream) {
+    return syncbn_bwd_apply_t<float>(dy, x, mean, rstd, gamma, beta, sums_all, R, n_global, dx, S, Bs, HW, C, act, stream,
+                                     (unsigned long long*)out_amax, out_epoch);
+}
+int dwc_bf16_syncbn_bwd_apply(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
+                              const float* beta, const float* sums_all, int R, long n_global, void* dx, int S, int Bs, int HW, int C,
+                              int act, void* stream) {
+    return syncbn_bwd_apply_t<dwc_bf16>((const dwc_bf16*)dy, (const dwc_bf16*)x, mean, rstd, gamma, beta, sums_all, R, n_global,
+                                        (dwc_bf16*)dx, S, Bs, HW, C, act, stream);
 }
 
 /* 1 when `act` is an activation code the instance-norm / layer-norm / linear_small entry points fuse (host only, no launch) */

@@ -230,6 +230,19 @@ SIGNATURES = {
     "dwc_batchnorm_bwd_amax": (c_int, [c_fp] * 9 + [c_int] * 6 + [c_fp, c_sz, c_fp, c_u, c_fp]),
     "dwc_bf16_batchnorm_fwd": (c_int, [c_fp] * 8 + [c_int] * 4 + [c_f, c_f, c_int, c_int, BnOrder, c_fp, c_sz, c_fp]),
     "dwc_bf16_batchnorm_bwd": (c_int, [c_fp] * 9 + [c_int] * 6 + [c_fp, c_sz, c_fp]),
+    # ---- synchronised batch norm: the phases between the ranks' exchanges (hipdwc.batchnorm, sync=; additive in ABI 11) ----
+    "dwc_syncbn_ws_bytes": (c_sz, [c_int] * 4),
+    "dwc_syncbn_moments": (c_int, [c_fp, c_fp] + [c_int] * 4 + [c_fp, c_sz, c_fp]),
+    "dwc_bf16_syncbn_moments": (c_int, [c_fp, c_fp] + [c_int] * 4 + [c_fp, c_sz, c_fp]),
+    "dwc_syncbn_finalise": (c_int, [c_fp, c_int] + [c_fp] * 4 + [c_int, c_int, c_f, c_f, BnOrder, c_fp]),
+    "dwc_syncbn_apply": (c_int, [c_fp] * 6 + [c_int] * 5 + [c_fp]),
+    "dwc_syncbn_apply_amax": (c_int, [c_fp] * 6 + [c_int] * 5 + [c_fp, c_u, c_fp]),
+    "dwc_bf16_syncbn_apply": (c_int, [c_fp] * 6 + [c_int] * 5 + [c_fp]),
+    "dwc_syncbn_bwd_sums": (c_int, [c_fp] * 9 + [c_int] * 5 + [c_fp, c_sz, c_fp]),
+    "dwc_bf16_syncbn_bwd_sums": (c_int, [c_fp] * 9 + [c_int] * 5 + [c_fp, c_sz, c_fp]),
+    "dwc_syncbn_bwd_apply": (c_int, [c_fp] * 7 + [c_int, ctypes.c_long, c_fp] + [c_int] * 5 + [c_fp]),
+    "dwc_syncbn_bwd_apply_amax": (c_int, [c_fp] * 7 + [c_int, ctypes.c_long, c_fp] + [c_int] * 5 + [c_fp, c_u, c_fp]),
+    "dwc_bf16_syncbn_bwd_apply": (c_int, [c_fp] * 7 + [c_int, ctypes.c_long, c_fp] + [c_int] * 5 + [c_fp]),
     # ---- plan queries of the im2col entry layer (ABI 11; host code only): out = int[4], see plan() ----
     "dwc_conv2d_fwd_plan": (c_int, [c_int] * 9 + [c_fp]),
     "dwc_conv2d_bwd_weight_plan": (c_int, [c_int] * 9 + [c_fp]),

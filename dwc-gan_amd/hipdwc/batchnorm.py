@@ -13,6 +13,9 @@ result does not depend on how many segments share the launch.
 ``DWC_BN_HIP=0`` (``BN_HIP``), and channel counts the kernels do not take (not a multiple of 4 fp32 / 8 bf16, more than 256 such
 groups) or more than 8 segments / updates, run the same segmented semantics on stock device ops -- ``F.batch_norm`` per segment, in
 ``order``: the A/B partner of the kernels (benchmarks/bn_overhead.py) and the only fallback.
+
+Under data parallel the statistics are per rank unless ``sync=`` is given: hipdwc.syncbn cuts the two kernel chains where
+per-(segment, channel) numbers exist and exchanges those between the ranks.
 """
 import ctypes
 import os
@@ -128,10 +131,15 @@ def _segmented_torch(x, weight, bias, running_mean, running_var, S, order, act, 
     return _act_torch(torch.cat(ys) if S > 1 else ys[0], act)
 
 
-def batch_norm(x, weight, bias, running_mean, running_var, segments=1, order=None, act="none", training=True, momentum=0.1, eps=1e-5):
+def batch_norm(x, weight, bias, running_mean, running_var, segments=1, order=None, act="none", training=True, momentum=0.1, eps=1e-5,
+               sync=None):
     """nn.BatchNorm2d (+ none / relu / lrelu(0.1)) on a batch of ``segments`` equal parts, each normalised as in a call of its own;
     ``order``: the segments whose statistics step the running buffers, in sequence (default every segment once).  ``training=False``:
-    the running buffers normalise the whole batch and are not written (segments / order do not matter)."""
+    the running buffers normalise the whole batch and are not written (segments / order do not matter).
+
+    ``sync`` (data parallel, hipdwc.syncbn): an object with ``world``, ``rank`` and ``all_gather``; a segment is then the union of the
+    ranks' parts of it and is normalised with the statistics of that union, identical bit for bit on every rank, as are the running
+    buffers.  ``order`` means the same; eval mode exchanges nothing; ``None``, or one rank without ``sync.force``, is the path above."""
     if momentum is None:
         raise NotImplementedError("batch_norm: momentum=None (cumulative moving average) is not built")
     if act not in ACTS:
@@ -147,8 +155,12 @@ def batch_norm(x, weight, bias, running_mean, running_var, segments=1, order=Non
         raise ValueError("batch_norm: order %s names a segment outside 0..%d" % (order, S - 1))
     if (running_mean is None) != (running_var is None):
         raise ValueError("batch_norm: running_mean and running_var come together")
+    synced = False
+    if training and sync is not None:
+        from . import syncbn
+        synced = syncbn.active(sync)
     if training:
-        if (B // S) * x.shape[2] * x.shape[3] < 2:
+        if not synced and (B // S) * x.shape[2] * x.shape[3] < 2:
             raise ValueError("Expected more than 1 value per channel when training, got input size %s in %d segment(s)" % (
                 list(x.shape), S))
     else:
@@ -157,6 +169,9 @@ def batch_norm(x, weight, bias, running_mean, running_var, segments=1, order=Non
         S, order = 1, ()
     if BN_HIP and not x.is_cuda:
         ops._require_device(x)
+    if synced:
+        return syncbn.sync_batch_norm(x, weight, bias, running_mean, running_var, S, order, act, momentum, eps, sync,
+                                      bool(BN_HIP and supported(x, S, len(order))))
     if BN_HIP and supported(x, S, len(order)):
         return _BatchNorm.apply(x, weight, bias, running_mean, running_var, S, order, ops.ACT[act], bool(training), float(momentum),
                                 float(eps))

@@ -3,10 +3,20 @@
 The reference is single-device; this is the new capability.  Every
 sample is independent through the conv/norm stack of the shipped configurations (IN/AdaIN per
 (n,c), LayerNorm per n) and every loss is a batch mean, so equal shards + gradient AVERAGING
-reproduce the global-batch gradient.  The exception is ``dis.norm: bn`` (hipdwc.batchnorm): batch
-statistics and running buffers are PER RANK -- there is no SyncBN, the reference being
-single-device -- so an N-rank run normalises each shard with its own statistics and the ranks'
-running buffers drift apart (``warn_per_rank_batchnorm`` says so once).  There is exactly one exchange per optimiser step: an all-reduce of
+reproduce the global-batch gradient.  The exception is ``dis.norm: bn`` (hipdwc.batchnorm): by default batch
+statistics and running buffers are PER RANK, so an N-rank run normalises each shard with its own
+statistics and the ranks' running buffers drift apart (``warn_per_rank_batchnorm`` says so once).
+``Solver.enable_data_parallel(sync_bn=True)`` / ``DWC_SYNC_BN=1`` closes the gap (hipdwc.syncbn): every
+batch-norm layer exchanges its per-(segment, channel) moments in the forward and its two coupling sums
+in the backward, one small all-gather each, merged in rank order, so that statistics, dx and the
+running buffers are those of the global batch and bit-identical on every rank.  Those all-gathers run
+on the SAME group as the gradient buckets, synchronously, from inside forward and backward.
+ASSUMPTION: every rank runs the same graph -- the same layers in the same order, and autograd's
+backward visits one discriminator's batch-norm nodes in the reverse of that order on every rank -- so
+the ranks issue their collectives (all-gathers and bucket all-reduces alike) in one agreed sequence.
+A rank that skipped a layer, or ran a different number of D passes, would pair its collective with
+another one's: a hang or wrong numbers, not an error message.
+Without batch norm there is exactly one exchange per optimiser step: an all-reduce of
 that optimiser's gradients (D: 13.99 M floats = 55.9 MB, G: 20.36 M = 81.4 MB at 128x128),
 packed into flat fp32 buckets so that RCCL sees a few large messages (xGMI is point-to-point:
 per-link bandwidth, not message rate, is the limit).
@@ -40,7 +50,7 @@ def warn_per_rank_batchnorm(bn_layers, group=None):
         return
     _BN_WARNED = True
     import warnings
-    warnings.warn("dis.norm 'bn' under data parallel: batch statistics and running buffers are per rank (no SyncBN); %d layers"
+    warnings.warn("dis.norm 'bn' under data parallel: batch statistics and running buffers are per rank (enable_data_parallel(sync_bn=True) / DWC_SYNC_BN=1 synchronises them); %d layers"
                   % len(bn_layers))
 
 

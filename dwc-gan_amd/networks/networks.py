@@ -77,7 +77,11 @@ class SegmentedBatchNorm2d(nn.BatchNorm2d):
     forward is hipdwc.batchnorm: ``segments`` = S equal parts of the batch, part s normalised with its own batch statistics -- the
     s-th of S consecutive calls of the reference's module -- and the running buffers stepped once per entry of ``stat_order``
     (default 0 .. S-1), in that sequence; ``num_batches_tracked`` counts those steps.  ``act``: none / relu / lrelu(0.1) fused into the
-    apply pass.  (The class name keeps ``weights_init`` away from it, as from nn.BatchNorm2d.)"""
+    apply pass.  (The class name keeps ``weights_init`` away from it, as from nn.BatchNorm2d.)  ``sync``: None, or the exchange
+    object of hipdwc.syncbn under data parallel (Solver.enable_data_parallel(sync_bn=True)): batch statistics over all ranks; not
+    part of the state_dict, and shared, not copied, by a deep copy of the module."""
+
+    sync = None
 
     def forward(self, x, act="none", segments=None, stat_order=None):
         S = int(segments or 1)
@@ -86,7 +90,7 @@ class SegmentedBatchNorm2d(nn.BatchNorm2d):
         if self.training and self.track_running_stats and order:
             self.num_batches_tracked.add_(len(order))
         return batchnorm.batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, segments=S, order=order, act=act,
-                                    training=training, momentum=self.momentum, eps=self.eps)
+                                    training=training, momentum=self.momentum, eps=self.eps, sync=self.sync)
 
 
 # --------------------------------------------------------------------------------------

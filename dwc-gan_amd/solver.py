@@ -106,21 +106,31 @@ class Solver(nn.Module):
                 param.requires_grad = False
 
     # ---- data parallel -----------------------------------------------------------------------
-    def enable_data_parallel(self, group=None, bucket_bytes=DP_BUCKET_BYTES):
+    def enable_data_parallel(self, group=None, bucket_bytes=DP_BUCKET_BYTES, sync_bn=None):
         """One process per GPU (torch.distributed initialised by the caller, backend nccl = RCCL): gradients of D / G become
-        views of flat buckets that are all-reduced (averaged) as backward completes them (hipdwc.dp.OverlappedGradReducer)."""
-        from hipdwc import dp
+        views of flat buckets that are all-reduced (averaged) as backward completes them (hipdwc.dp.OverlappedGradReducer).
+        ``sync_bn`` (None: the environment's DWC_SYNC_BN, default 0): the batch-norm layers of D (dis.norm 'bn') take their batch
+        statistics over all ranks (hipdwc.syncbn: two small all-gathers per layer and pass on the same group); off, they stay per
+        rank and a warning says so."""
+        from hipdwc import dp, syncbn
         self._reducers = {"dis": dp.OverlappedGradReducer(self.dis_opt.param_groups[0]["params"], group, bucket_bytes),
                           "gen": dp.OverlappedGradReducer(self.gen_opt.param_groups[0]["params"], group, bucket_bytes)}
         self.grad_sync = None
-        dp.warn_per_rank_batchnorm(self.dis.bn_layers(), group)
+        if sync_bn is None:
+            sync_bn = os.environ.get("DWC_SYNC_BN", "0") == "1"
+        force = os.environ.get("DWC_FORCE_DP") == "1"
+        if sync_bn:
+            for m in self.dis.bn_layers():
+                m.sync = syncbn.GroupSync(group, force=force)
+        else:
+            dp.warn_per_rank_batchnorm(self.dis.bn_layers(), group)
         # the persistent LSTM launches need ALL their workgroups resident while RCCL's all-reduce kernels (launched from inside
         # backward on a side stream) hold CUs of their own: keep those launches to half of a 256-CU device; larger grids take the
         # per-step kernels (dwc_lstm_seq_* return DWC_EINVAL above the cap)
         # (half of THIS device's CUs, not a constant: on a part with <= 128 CUs or in CPX mode "128" would cap nothing)
         if self.device.type == "cuda":
             ops.LSTM_SEQ_MAX_WORKGROUPS = max(1, torch.cuda.get_device_properties(self.device).multi_processor_count // 2)
-        if os.environ.get("DWC_FORCE_DP") == "1":
+        if force:
             for r in self._reducers.values():
                 r.force = True
 

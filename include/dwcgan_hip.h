@@ -837,6 +837,50 @@ int dwc_bf16_batchnorm_bwd(const void* dy, const void* x, const float* mean, con
                            const float* beta, void* dx, float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act,
                            int training, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- synchronised batch norm under data parallel (hipdwc.batchnorm, sync=; additive in ABI 11) ----
+ * The two chains above cut at the points where per-(segment, channel) numbers exist, so that R ranks can exchange them (all-gather,
+ * rank order) and every rank computes bit-identical statistics, buffers and coupling terms.  Each rank holds Bs samples of each of
+ * the S segments; a segment is the union of the ranks' parts.  Same shape rules as dwc_batchnorm_* except that Bs * HW == 1 is
+ * legal: the count that must reach 2 is the segment's over all ranks, which the caller checks.  Nothing allocates or synchronises.
+ *   _moments:   moments[3][S][C] = (count, mean, M2) of this rank's part of each segment (the statistics pass and the per-segment
+ *               Chan merge of dwc_batchnorm_fwd, stopped before rstd).  Scratch: dwc_syncbn_ws_bytes.
+ *   _finalise:  moments_all[R][3][S][C] (the gathered moments, rank order) merged per (segment, channel) in rank order -> mean[S][C],
+ *               rstd[S][C] = 1 / sqrt(M2 / cnt + eps); running buffers (NULL: skipped) stepped through `order` with the unbiased
+ *               variance M2 / (cnt - 1), as dwc_batchnorm_fwd steps them.  R = 1 reproduces dwc_batchnorm_fwd's statistics bit
+ *               for bit.  DWC_EINVAL: R < 1, S outside 1..8, C < 1, order.n outside 0..8, an order entry outside 0..S-1.
+ *   _apply:     y = act((x - mean[s]) * rstd[s] * gamma + beta) with the caller's statistics (act none / relu / lrelu).
+ *   _bwd_sums:  sums[2][S][C] = (sum g, sum g * xhat) over this rank's part of each segment; dgamma / dbeta (NULL: skipped) = those
+ *               added over the segments: sums over THIS rank's samples, averaged between ranks like any parameter gradient.
+ *   _bwd_apply: sums_all[R][2][S][C] (gathered, rank order) added in rank order, n_global = elements per channel of a whole segment
+ *               over all ranks (>= 2): dx = gamma * rstd * (g - sum g / n_global - xhat * sum g xhat / n_global).
+ * The _amax forms (fp32) raise the absmax slot of y / dx. */
+size_t dwc_syncbn_ws_bytes(int S, int Bs, int HW, int C);
+int dwc_syncbn_moments(const float* x, float* moments, int S, int Bs, int HW, int C, void* ws, size_t ws_bytes, void* stream);
+int dwc_bf16_syncbn_moments(const void* x, float* moments, int S, int Bs, int HW, int C, void* ws, size_t ws_bytes, void* stream);
+int dwc_syncbn_finalise(const float* moments_all, int R, float* mean, float* rstd, float* running_mean, float* running_var, int S,
+                        int C, float eps, float momentum, dwc_bn_order order, void* stream);
+int dwc_syncbn_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* y, int S,
+                     int Bs, int HW, int C, int act, void* stream);
+int dwc_syncbn_apply_amax(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* y, int S,
+                          int Bs, int HW, int C, int act, void* out_amax, unsigned out_epoch, void* stream);
+int dwc_bf16_syncbn_apply(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, void* y, int S,
+                          int Bs, int HW, int C, int act, void* stream);
+int dwc_syncbn_bwd_sums(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                        float* sums, float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act, void* ws, size_t ws_bytes,
+                        void* stream);
+int dwc_bf16_syncbn_bwd_sums(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
+                             const float* beta, float* sums, float* dgamma, float* dbeta, int S, int Bs, int HW, int C, int act,
+                             void* ws, size_t ws_bytes, void* stream);
+int dwc_syncbn_bwd_apply(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                         const float* sums_all, int R, long n_global, float* dx, int S, int Bs, int HW, int C, int act,
+                         void* stream);
+int dwc_syncbn_bwd_apply_amax(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                              const float* beta, const float* sums_all, int R, long n_global, float* dx, int S, int Bs, int HW, int C,
+                              int act, void* out_amax, unsigned out_epoch, void* stream);
+int dwc_bf16_syncbn_bwd_apply(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
+                              const float* beta, const float* sums_all, int R, long n_global, void* dx, int S, int Bs, int HW, int C,
+                              int act, void* stream);
+
 /* ---- text encoder: the data movement around its bi-LSTM layers in one launch each (additive in ABI 11; csrc/txt_glue.hip,
  *      DESIGN.md 18; reference networks_v2.py:199-249) ---------------------------------------------------------------------------------
  * All tensors fp32 and dense.  j is a sample's position in the length-sorted batch; order[j] its position in the caller's batch,
