@@ -4,7 +4,11 @@ B = 16, fp32) and the c2 shape (128x128, B = 128, bf16).  One process, one train
 ``--rounds`` windows of ``--steps`` dis_update calls each (device events around the window), so that the run-to-run spread of a
 variant (max - min over its windows) stands beside every difference between two variants.
 
-    python benchmarks/penalty_overhead.py [--steps 10] [--warmup 3] [--rounds 3] [--configs c1,c2] [--out profiles/penalty_overhead.json]
+    python benchmarks/penalty_overhead.py [--steps 10] [--warmup 3] [--rounds 3] [--configs c1,c2] [--norm none|in|ln]
+                                          [--out profiles/penalty_overhead.json]
+
+``--norm in / ln`` sets ``dis.norm``: the HIP branch is then hipdwc.normjvp (the tangent of the norm), the torch branch
+the double backward through the norm.
 """
 import argparse
 import contextlib
@@ -40,11 +44,12 @@ def window(tr, batch, cfg, hip, steps, it0):
     return a.elapsed_time(b) / steps
 
 
-def measure(conf, steps, warmup, rounds):
+def measure(conf, steps, warmup, rounds, norm="none"):
     S, B, precision = SHAPES[conf]
     ops.set_precision(precision)
     dev = torch.device("cuda:0")
     base = synth.make_config(image_size=S)
+    base["dis"]["norm"] = norm                        # (in / ln: the HIP branch is hipdwc.normjvp, the tangent of the norm)
     torch.manual_seed(1)
     with contextlib.redirect_stdout(io.StringIO()):
         tr = Solver(base, dev, None).to(dev)
@@ -65,7 +70,7 @@ def measure(conf, steps, warmup, rounds):
     ops.set_precision("fp32")
     rows = []
     for (name, hip), ms in times.items():
-        rows.append({"config": conf, "batch": B, "precision": precision, "penalty": name, "penalty_hip": hip,
+        rows.append({"config": conf, "batch": B, "precision": precision, "dis_norm": norm, "penalty": name, "penalty_hip": hip,
                      "d_step_ms_windows": [round(m, 3) for m in ms], "d_step_ms_median": round(statistics.median(ms), 3),
                      "spread_ms": round(max(ms) - min(ms), 3)})
     return rows
@@ -77,16 +82,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--configs", default="c1,c2")
+    ap.add_argument("--norm", default="none", choices=["none", "in", "ln"], help="dis.norm of the discriminator under the penalties")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     default = ops.PENALTY_HIP
     rows = []
     try:
         for conf in args.configs.split(","):
-            part = measure(conf, args.steps, args.warmup, args.rounds)
+            part = measure(conf, args.steps, args.warmup, args.rounds, args.norm)
             med = {(r["penalty"], r["penalty_hip"]): r["d_step_ms_median"] for r in part}
             for name in ("r1", "gp"):
-                part.append({"config": conf, "penalty": name, "hip_over_torch_d_step": round(med[(name, 1)] / med[(name, 0)], 4),
+                part.append({"config": conf, "dis_norm": args.norm, "penalty": name, "hip_over_torch_d_step": round(med[(name, 1)] / med[(name, 0)], 4),
                              "added_ms_torch": round(med[(name, 0)] - med[("none", 1)], 3),
                              "added_ms_hip": round(med[(name, 1)] - med[("none", 1)], 3)})
             for r in part:
@@ -96,7 +102,7 @@ def main():
         ops.PENALTY_HIP = default
     if args.out:
         with open(args.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup, "rounds": args.rounds,
+            json.dump({"device": torch.cuda.get_device_name(0), "dis_norm": args.norm, "steps": args.steps, "warmup": args.warmup, "rounds": args.rounds,
                        "rows": rows}, f, indent=1)
             f.write("\n")
 

@@ -222,6 +222,11 @@ SIGNATURES = {
     "dwc_grad_penalty_fwd": (c_int, [c_fp] * 4 + [c_int] * 5 + [c_fp]),
     "dwc_grad_penalty_scale": (c_int, [c_fp] * 4 + [c_int] * 4 + [c_fp]),
     "dwc_src_head_seed": (c_int, [c_fp] * 3 + [c_int] * 3 + [c_fp]),
+    # ---- tangent of instance norm / MUNIT LayerNorm and its backward (hipdwc.normjvp) ----
+    "dwc_norm_tangent_ws_bytes": (c_sz, [c_int] * 4),
+    "dwc_norm_tangent_stats_elems": (c_sz, [c_int] * 3),
+    "dwc_norm_tangent_fwd": (c_int, [c_fp] * 5 + [c_int] * 4 + [c_f, c_fp, c_sz, c_fp]),
+    "dwc_norm_tangent_bwd": (c_int, [c_fp] * 8 + [c_int] * 4 + [c_fp, c_sz, c_fp]),
     # ---- batch norm over S equal batch segments (hipdwc.batchnorm) ----
     "dwc_batchnorm_ws_bytes": (c_sz, [c_int] * 4),
     "dwc_batchnorm_fwd": (c_int, [c_fp] * 8 + [c_int] * 4 + [c_f, c_f, c_int, c_int, BnOrder, c_fp, c_sz, c_fp]),

@@ -586,7 +586,7 @@ ZERO_PAD_HIP = int(os.environ.get("DWC_ZERO_PAD_HIP", "1"))   # Conv2dBlock pad_
 RING_FUSED = int(os.environ.get("DWC_RING_FUSED", "1"))   # stride-1 data gradients: border ring inside the halo launch (0: strip GEMM + fold launches)
 # gradient / R1 penalties of the D step on the closed-form second derivative over the HIP convolutions (hipdwc.penalty) where the
 # discriminator allows it (MsImageDis.penalty_hip_ok); 0: always torch's double backward (MsImageDis.forward_src_scale0_torch).
-# Opt-in: neither form has been timed at the c1 / c2 shapes yet (benchmarks/penalty_overhead.py).
+# Opt-in: norm none has not been timed at the c1 / c2 shapes yet (benchmarks/penalty_overhead.py); norm in / ln run on hipdwc.normjvp.
 PENALTY_HIP = int(os.environ.get("DWC_PENALTY_HIP", "0"))
 # dis.gan_type nsgan / wgan on the one-launch loss tails (adv_tail, dwc_adv_tail_gan_*).  0: they take the term-by-term torch algebra of
 # MsImageDis.dis_loss_terms / gen_loss_terms, as before the tails took them -- the A/B partner of benchmarks/gan_tail_overhead.py.

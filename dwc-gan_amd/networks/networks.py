@@ -494,8 +494,10 @@ class MsImageDis(nn.Module):
         """The first scale's 'src' map -- ``self(x, False)[0][0]`` -- on stock torch device ops (F.pad / F.conv2d / activation), for the
         two callers that differentiate it TWICE: Solver.gradient_penalty / r1_penalty (reference solver.py:291-315,338-350; off in the
         shipped configuration).  The HIP autograd Functions are once-differentiable; these penalties are an O(B) side branch of the D
-        step, so they take torch's own double backward on the same parameters instead.  x: [B, 3, H, W] fp32."""
-        if self.norm not in ("none", "sn") or self.pad_type not in ("reflect", "zero", "replicate"):
+        step, so they take torch's own double backward on the same parameters instead.  x: [B, 3, H, W] fp32.
+        ``dis.norm`` in / ln: ``F.instance_norm`` / MUNIT's LayerNorm expression (reference networks.py:736-752: per-sample mean and
+        unbiased std, the whole batch as one sample at batch 1) behind the convolutions of layers 2 .. n_layer, as in _make_net."""
+        if self.norm not in ("none", "sn", "in", "ln") or self.pad_type not in ("reflect", "zero", "replicate"):
             raise NotImplementedError("gradient penalties: discriminator norm %r / pad %r" % (self.norm, self.pad_type))
         mode = {"reflect": "reflect", "zero": "constant", "replicate": "replicate"}[self.pad_type]
         # norm 'sn': this call is one reference call on scale 0 -- one iteration of its SN layers (HIP), then W_bar / sigma in torch
@@ -510,6 +512,13 @@ class MsImageDis(nn.Module):
             else:
                 w, b = blk.conv.weight, blk.conv.bias
             h = F.conv2d(F.pad(h, (p, p, p, p), mode=mode) if p else h, w, b, stride=blk.stride)
+            if blk.norm_kind == "in":
+                h = F.instance_norm(h, eps=blk.norm.eps)
+            elif blk.norm_kind == "ln":
+                flat = h.reshape(1 if h.size(0) == 1 else h.size(0), -1)          # (batch 1: one group either way)
+                h = (h - flat.mean(1).reshape(-1, 1, 1, 1)) / (flat.std(1).reshape(-1, 1, 1, 1) + blk.norm.eps)
+                if blk.norm.affine:
+                    h = h * blk.norm.gamma.reshape(1, -1, 1, 1) + blk.norm.beta.reshape(1, -1, 1, 1)
             if blk.act_kind == "relu":
                 h = torch.relu(h)
             elif blk.act_kind == "lrelu":
@@ -519,10 +528,13 @@ class MsImageDis(nn.Module):
         return F.conv2d(h, self.cnns_src[0].weight, self.cnns_src[0].bias)
 
     def penalty_hip_ok(self):
-        """Whether the penalties of this discriminator have the closed-form second derivative of hipdwc.penalty: no normalisation
-        (the rank-one sigma term of 'sn' is not built), reflect padding, a piecewise-linear activation, channel counts the
-        pointwise passes take."""
-        from hipdwc import penalty
+        """Whether the penalties of this discriminator run on the HIP kernels: reflect padding, a piecewise-linear activation,
+        channel counts the pointwise passes take, and either no normalisation (the closed-form second derivative of hipdwc.penalty)
+        or ``norm`` in / ln with channel counts the tangent kernels take (hipdwc.normjvp).  The rank-one sigma term of 'sn' is not
+        built; 'bn' has no penalty branch at all."""
+        from hipdwc import normjvp, penalty
+        if self.norm in normjvp.KINDS:
+            return normjvp.supported(self)
         blocks = list(self.cnns_feat[0])
         return (self.norm == "none" and self.pad_type == "reflect" and self.activ in penalty.ACTS
                 and penalty.supported([blk.conv.weight for blk in blocks], [blk.act_kind for blk in blocks]))
@@ -530,8 +542,10 @@ class MsImageDis(nn.Module):
     def src_grad_penalty(self, x, mode):
         """The gradient penalty (mode "gp") / R1 penalty (mode "r1") of the first scale's 'src' map at x -- the value of
         Solver.gradient_penalty / r1_penalty on forward_src_scale0_torch(x) -- on the HIP kernels, differentiable w.r.t. this
-        scale's convolution weights (hipdwc.penalty).  x: [B, 3, H, W] fp32 or an fp32 NHWC4 image buffer."""
-        from hipdwc import penalty
+        scale's parameters (hipdwc.penalty; ``norm`` in / ln: hipdwc.normjvp).  x: [B, 3, H, W] fp32 or an fp32 NHWC4 image buffer."""
+        from hipdwc import normjvp, penalty
+        if self.norm in normjvp.KINDS:
+            return normjvp.src_grad_penalty(self, x, mode)
         return penalty.src_grad_penalty(self, x, mode)
 
     def _classification_loss(self, logit, target, dataset="CelebA"):

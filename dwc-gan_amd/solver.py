@@ -314,7 +314,8 @@ class Solver(nn.Module):
         # Gradient / R1 penalties (reference solver.py:337-350; gp_w 0 and use_r1 False in the shipped configuration).  Both differentiate
         # the first scale's src map w.r.t. its INPUT and then that gradient w.r.t. D's weights.  The HIP Functions are once-differentiable:
         # with ops.PENALTY_HIP, and a discriminator whose second derivative has the closed form (MsImageDis.penalty_hip_ok: norm none,
-        # reflect padding, lrelu / relu / none), the penalty is one Function over the HIP convolutions (hipdwc.penalty); anything else
+        # reflect padding, lrelu / relu / none), the penalty is one Function over the HIP convolutions (hipdwc.penalty); with norm in /
+        # ln it is one Function over the same convolutions, the norms and the tangent of the norm (hipdwc.normjvp); anything else
         # takes torch's double backward on stock device ops over the same parameters (MsImageDis.forward_src_scale0_torch).
         # The reference adds them IN PLACE to the tensor both names refer to (`self.loss_dis_all = self.loss_dis; ... += ...`): loss_dis
         # reads the penalised value afterwards too; kept.

@@ -794,6 +794,29 @@ int dwc_grad_penalty_scale(const float* g, const float* k, const float* dout, fl
  * the sum of the 1x1 'src' head's map w.r.t. the pre-activation of the layer below it, in one pass.  C a multiple of 4. */
 int dwc_src_head_seed(const float* a, const float* w_s, float* d, int rows, int C, int act, void* stream);
 
+/* ---- tangent (forward-mode derivative) of instance norm / MUNIT LayerNorm and its backward (csrc/norm_tangent.hip, DESIGN.md 23;
+ *      ABI 11, additive) -- the once-differentiable op through which the penalties above reach a discriminator with dis.norm in / ln.
+ * z, zdot, out, dout, dz, dzdot: fp32 [B][HW][C] NHWC.  Per normalisation group (kind DWC_NORM_TANGENT_IN: one (n, c), M = HW,
+ * r = (biased variance + eps)^-1/2, lam = r / M, rho = 1; DWC_NORM_TANGENT_LN: one sample, M = C * HW, s = unbiased std,
+ * r = 1 / (s + eps), lam = 1 / ((M - 1) s), rho = (s + eps) / s), with xh = r (z - mean z), cd = zdot - mean zdot, A = <xh, cd>:
+ *   forward    out = gamma[c] (r cd - lam A xh)                     gamma: [C] or NULL (= 1); must be NULL for kind IN
+ *   backward   u = gamma[c] dout, ub = mean u, U = <u, xh>, Cu = <u, cd>
+ *              dzdot = r (u - ub) - lam U xh
+ *              dz    = -lam r (Cu xh + U cd + A (u - ub)) + (2 + rho) lam^2 A U xh
+ *              dgamma[c] = sum over samples and pixels of dout (r cd - lam A xh)      (kind LN; may be NULL; must be NULL for kind IN)
+ * stats: dwc_norm_tangent_stats_elems(kind, B, C) floats, an OUTPUT of the forward kept for the backward (six planes of one value per
+ * group: mean z, r, mean zdot, A, lam, rho).  Sums are taken about the group's first element and combined from per-chunk partials
+ * in caller scratch in a fixed order (no atomics: bit-identical run to run).  C a power of two, 4 .. 1024, else DWC_EINVAL before
+ * any launch (dwc_norm_tangent_ws_bytes answers 0); ws >= dwc_norm_tangent_ws_bytes, else DWC_EWORKSPACE. */
+#define DWC_NORM_TANGENT_IN 0
+#define DWC_NORM_TANGENT_LN 1
+size_t dwc_norm_tangent_ws_bytes(int kind, int B, int HW, int C);
+size_t dwc_norm_tangent_stats_elems(int kind, int B, int C);
+int dwc_norm_tangent_fwd(const float* z, const float* zdot, const float* gamma, float* out, float* stats, int kind, int B, int HW, int C,
+                         float eps, void* ws, size_t ws_bytes, void* stream);
+int dwc_norm_tangent_bwd(const float* dout, const float* z, const float* zdot, const float* gamma, const float* stats, float* dz,
+                         float* dzdot, float* dgamma, int kind, int B, int HW, int C, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- batch normalisation over S equal batch segments (ABI 10; reference networks.py:547 nn.BatchNorm2d inside Conv2dBlock;
  *      csrc/norm.hip) ---------------------------------------------------------------------------------------------
  * x, y, dy, dx: [S * Bs][HW][C] NHWC, fp32 or bf16; segment s = samples s * Bs ... (s + 1) * Bs - 1 behaves like the s-th of S
