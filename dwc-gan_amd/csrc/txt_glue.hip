@@ -73,6 +73,61 @@ __global__ __launch_bounds__(256) void txt_operand_bwd_kernel(const float* __res
     if (idx && threadIdx.x == 0) idx[row] = tokens[(size_t)src * seq_len + t];
 }
 
+// The same operand from the CALLER'S embedded words instead of a table lookup (TxtEncoder.forward_embed): emb is [B][seq_len][E] in
+// caller order, lens the sorted lengths.  A slot with t >= lens[j] is a SELECT of 0: what the caller left there is never loaded,
+// so neither a NaN nor an Inf behind a sample's length reaches X (and through dw_ih = dG^T X a gradient).  On a table whose padding
+// row is zero this is txt_operand_fwd_kernel's output bit for bit.  grid t_max * B, 256 threads.
+__global__ __launch_bounds__(256) void txt_operand_embed_fwd_kernel(const float* __restrict__ emb, const int* __restrict__ order,
+                                                                    const int* __restrict__ lens, const float* __restrict__ mask,
+                                                                    const float* __restrict__ style, float* __restrict__ X, int B,
+                                                                    int seq_len, int E, int S) {
+    const int row = blockIdx.x, t = row / B, j = row - t * B;
+    const int src = txt_perm(order, j, B);
+    const bool live = t < lens[j];
+    const float* e = emb + ((size_t)src * seq_len + t) * E;
+    const float* m = mask ? mask + (size_t)row * E : nullptr;
+    float* x = X + (size_t)row * (E + S);
+    for (int k = threadIdx.x; k < E; k += 256) {
+        float v = 0.f;
+        if (live) v = m ? e[k] * m[k] : e[k];
+        x[k] = v;
+    }
+    const float* s = style + (size_t)src * S;
+    for (int k = threadIdx.x; k < S; k += 256) x[E + k] = s[k];
+}
+
+// Its adjoint.  d_emb is the gradient of the caller's tensor itself, [B][seq_len][E] in CALLER order: block (t, j) owns row
+// (order[j], t), so every element is written once -- dX[t][j][:E] * mask where t < min(t_max, lens[j]), +0.0 elsewhere.  d_cat is
+// what txt_operand_bwd_kernel writes (the style-row sum stays the caller's reduction).  One block per slot of the FULL
+// [seq_len][B] grid, 256 threads.
+__global__ __launch_bounds__(256) void txt_operand_embed_bwd_kernel(const float* __restrict__ dxa, const float* __restrict__ dxb,
+                                                                    const int* __restrict__ order, const int* __restrict__ lens,
+                                                                    const float* __restrict__ mask, float* __restrict__ d_cat,
+                                                                    float* __restrict__ d_emb, int t_max, int B, int seq_len, int E,
+                                                                    int S) {
+    const int row = blockIdx.x, t = row / B, j = row - t * B, I = E + S;
+    const int src = txt_perm(order, j, B);
+    const bool live = t < t_max;
+    const size_t in = (size_t)row * I;                          // (read only where live: dxa / dxb end at t_max)
+    if (d_emb) {
+        const bool own = live && t < lens[j];
+        const float* m = mask ? mask + (size_t)row * E : nullptr;
+        float* o = d_emb + ((size_t)src * seq_len + t) * E;
+        for (int k = threadIdx.x; k < E; k += 256) {
+            float g = 0.f;
+            if (own) {
+                g = dxb ? dxa[in + k] + dxb[in + k] : dxa[in + k];
+                if (m) g = __fmul_rn(g, m[k]);
+            }
+            o[k] = g;
+        }
+    }
+    if (d_cat) {
+        float* o = d_cat + ((size_t)t * B + src) * I + E;
+        for (int k = threadIdx.x; k < S; k += 256) o[k] = live ? (dxb ? dxa[in + E + k] + dxb[in + E + k] : dxa[in + E + k]) : 0.f;
+    }
+}
+
 // The state entering each step of a layer, for its recurrent weight gradient: hprev[0][t] = out[0][t-1], hprev[1][t] = out[1][t+1],
 // zeros at the two ends (out is zero past each sample's length, so the reverse direction starts from zeros at its own last token).
 // grid (T * B, 2), 256 threads.
@@ -179,6 +234,28 @@ int dwc_txt_operand_bwd(const float* dxa, const float* dxb, const long long* tok
         return DWC_EINVAL;
     hipLaunchKernelGGL(txt_operand_bwd_kernel, dim3(seq_len * B), dim3(256), 0, (hipStream_t)stream, dxa, dxb, tokens, order, mask,
                        d_cat, d_emb, idx, t_max, B, seq_len, E, S);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+
+int dwc_txt_operand_embed_fwd(const float* emb, const int* order, const int* lens, const float* mask, const float* style, float* x,
+                              int t_max, int B, int seq_len, int E, int S, void* stream) {
+    if (!emb || !order || !lens || !x || (S > 0 && !style) || seq_len < 1 || t_max < 1 || t_max > seq_len || B < 1 || E < 1 || S < 0 ||
+        (long long)seq_len * B > 0x7fffffffLL)
+        return DWC_EINVAL;
+    hipLaunchKernelGGL(txt_operand_embed_fwd_kernel, dim3(t_max * B), dim3(256), 0, (hipStream_t)stream, emb, order, lens, mask, style,
+                       x, B, seq_len, E, S);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+
+int dwc_txt_operand_embed_bwd(const float* dxa, const float* dxb, const int* order, const int* lens, const float* mask, float* d_cat,
+                              float* d_emb, int t_max, int B, int seq_len, int E, int S, void* stream) {
+    if (!dxa || !order || !lens || (!d_cat && !d_emb) || seq_len < 1 || t_max < 1 || t_max > seq_len || B < 1 || E < 1 || S < 0 ||
+        (d_cat && S < 1) || (long long)seq_len * B > 0x7fffffffLL)
+        return DWC_EINVAL;
+    hipLaunchKernelGGL(txt_operand_embed_bwd_kernel, dim3(seq_len * B), dim3(256), 0, (hipStream_t)stream, dxa, dxb, order, lens, mask,
+                       d_cat, d_emb, t_max, B, seq_len, E, S);
     DWC_LAUNCH_CHECK();
     return DWC_OK;
 }

@@ -276,6 +276,9 @@ SIGNATURES = {
     "dwc_txt_inter_bwd": (c_int, [c_fp] * 7 + [c_int, c_fp] + [c_int] * 3 + [c_fp]),
     "dwc_txt_states_fwd": (c_int, [TxtLayers, c_fp, c_fp, c_fp] + [c_int] * 3 + [c_fp]),
     "dwc_txt_states_bwd": (c_int, [c_fp, c_fp, c_fp, TxtLayers] + [c_int] * 3 + [c_fp]),
+    # ---- the layer-1 operand from dense word embeddings (TxtEncoder.forward_embed; additive in ABI 11) ----
+    "dwc_txt_operand_embed_fwd": (c_int, [c_fp] * 6 + [c_int] * 5 + [c_fp]),
+    "dwc_txt_operand_embed_bwd": (c_int, [c_fp] * 7 + [c_int] * 5 + [c_fp]),
 }
 
 ABI_VERSION = 11             # DWC_ABI_VERSION of include/dwcgan_hip.h

@@ -1,6 +1,7 @@
 """The text encoder's data movement on the kernels of csrc/txt_glue.hip (C ABI ``dwc_txt_*`` in include/dwcgan_hip.h).
 
-``encode`` is what ``networks_v2.TxtEncoder.forward`` runs when ``ops.TXT_FUSED`` is set: the same values, random draws and
+``encode`` is what ``networks_v2.TxtEncoder.forward`` (and, on the caller's own word vectors, ``forward_embed``) runs when
+``ops.TXT_FUSED`` is set: the same values, random draws and
 gradients as its stock-tensor-op path, with ONE launch each for the layer-1 operand, the tensor between two layers and the final
 states, and one each for their adjoints (the two sums of the backward -- style rows over t, table rows per token id -- stay
 torch's reductions on the inputs they had, which keeps a run's bits).  The whole stack of layers is a single autograd node (``_TxtStack``): its backward calls
@@ -76,6 +77,39 @@ def operand_bwd(dxa, dxb, tokens, order, mask, E, vocab, padding_idx, need_style
     return d_style, d_table
 
 
+def operand_embed_fwd(emb, order, lens, mask, style, t_max):
+    """X:[t_max,B,E+S] in length-sorted order from the caller's embedded words.  emb: [B,seq_len,E] in caller order; lens: the sorted
+    lengths; rows behind a sample's length are zeros whatever emb holds there (a select: NaN / Inf included)."""
+    B, seq_len, E = _f32(emb).shape
+    S = style.shape[1]
+    assert 1 <= t_max <= seq_len
+    assert mask is None or (_f32(mask).shape[0] >= t_max and mask.shape[1:] == (B, E))
+    x = torch.empty((t_max, B, E + S), dtype=torch.float32, device=emb.device)
+    _lib.check(_lib.load().dwc_txt_operand_embed_fwd(emb.data_ptr(), _i32(order, B).data_ptr(), _i32(lens, B).data_ptr(), _p(mask),
+                                                     _f32(style, (B, S)).data_ptr(), x.data_ptr(), t_max, B, seq_len, E, S, _stream()),
+               "txt_operand_embed_fwd")
+    return x
+
+
+def operand_embed_bwd(dxa, dxb, order, lens, mask, E, seq_len, need_style=True, need_emb=True):
+    """(d_style [B,S] in caller order, d_emb [B,seq_len,E] in caller order) from dX = dxa + dxb (dxb may be None), None where not
+    needed.  d_emb is written once, by the one launch (zeros behind each length and from t_max on); the style rows are summed by the
+    reduction of ``operand_bwd``, on the tensor that launch lays out for it."""
+    t_max, B, I = dxa.shape
+    S = I - E
+    _f32(dxa)
+    assert dxb is None or _f32(dxb).shape == dxa.shape
+    if not (need_style or need_emb):
+        return None, None
+    dev = dxa.device
+    d_cat = torch.empty((seq_len, B, I), dtype=torch.float32, device=dev) if need_style else None     # (columns E.. are written)
+    d_emb = torch.empty((B, seq_len, E), dtype=torch.float32, device=dev) if need_emb else None
+    _lib.check(_lib.load().dwc_txt_operand_embed_bwd(dxa.data_ptr(), _p(dxb), _i32(order, B).data_ptr(), _i32(lens, B).data_ptr(),
+                                                     _p(mask), _p(d_cat), _p(d_emb), t_max, B, seq_len, E, S, _stream()),
+               "txt_operand_embed_bwd")
+    return (d_cat[:, :, E:].sum(0) if need_style else None), d_emb
+
+
 def _mask_args(mask, mask_row, T, B, H):
     if mask is None:
         return None, None
@@ -137,16 +171,21 @@ def states_bwd(d_feat, order, last, T, H, need_out):
 
 class _Plan:
     """What one call of ``encode`` fixes outside the differentiable inputs: indices, masks, sizes, cache owners."""
-    __slots__ = ("tokens", "order", "unsort", "lens", "last", "t_max", "mask_in", "masks", "mask_rows", "owners_ih", "owners_hh", "owners_b",
+    __slots__ = ("dense", "tokens", "order", "unsort", "lens", "last", "t_max", "mask_in", "masks", "mask_rows", "owners_ih", "owners_hh", "owners_b",
                  "padding_idx", "layers")
 
 
 class _TxtStack(torch.autograd.Function):
-    """(embedding table, style rows, stacked LSTM parameters of every layer) -> feat [B, 4*L*H]."""
+    """(source of layer 1, style rows, stacked LSTM parameters of every layer) -> feat [B, 4*L*H].  The source is the embedding
+    table, looked up at ``plan.tokens``, or -- ``plan.dense`` -- the caller's embedded words [B,seq_len,E] themselves; its gradient
+    comes back in the same slot."""
 
     @staticmethod
     def forward(ctx, plan, table, style, *params):
-        data = operand_fwd(table, plan.tokens, plan.order, plan.mask_in, style.contiguous(), plan.t_max)
+        if plan.dense:
+            data = operand_embed_fwd(table, plan.order, plan.lens, plan.mask_in, style.contiguous(), plan.t_max)
+        else:
+            data = operand_fwd(table, plan.tokens, plan.order, plan.mask_in, style.contiguous(), plan.t_max)
         outs, cs, saved = [], [], []
         for l in range(plan.layers):
             out, c, sv = ops.lstm_layer_fwd(data, plan.lens, *params[4 * l:4 * l + 4], owners=plan.owners_ih[l],
@@ -180,20 +219,26 @@ class _TxtStack(torch.autograd.Function):
             grads[4 * l:4 * l + 4] = [dw_ih, dw_hh, db, db]
             if l > 0:
                 d_out = inter_bwd(dx[0], dx[1], plan.masks[l - 1], plan.mask_rows[l - 1], d_feat, plan.order, plan.last, l - 1, H)
+            elif need_x and plan.dense:
+                d_style, d_table = operand_embed_bwd(dx[0], dx[1], plan.order, plan.lens, plan.mask_in, ctx.table_shape[2],
+                                                     ctx.table_shape[1], need_style=need[2], need_emb=need[1])
             elif need_x:
                 d_style, d_table = operand_bwd(dx[0], dx[1], plan.tokens, plan.order, plan.mask_in, ctx.table_shape[1],
                                                ctx.table_shape[0], plan.padding_idx, need_style=need[2], need_table=need[1])
         return (None, d_table, d_style) + tuple(grads)
 
 
-def encode(enc, style_ord, src_tokens, src_lengths, packed_index):
+def encode(enc, style_ord, src_tokens, src_lengths, packed_index, embeddings=None):
     """feat:[B, 4*L*H] of ``networks_v2.TxtEncoder`` ``enc`` for the caller's style rows, tokens [B,seq_len] and lengths [B].
-    ``packed_index(lens_sorted, t_max, bsz, device)``: row of a PackedSequence's data that holds each (t, b) slot."""
+    ``packed_index(lens_sorted, t_max, bsz, device)``: row of a PackedSequence's data that holds each (t, b) slot.
+    ``embeddings`` (then ``src_tokens`` is None): the embedded words [B,seq_len,E] themselves, dense fp32 on the device, take the
+    place of the table lookup (``TxtEncoder.forward_embed``); indices, draws and owners are the ones of the token path."""
     if enc.num_layers > MAX_LAYERS:
         raise ValueError("the text encoder's kernels take up to %d LSTM layers (DWC_TXT_MAX_LAYERS), got %d" % (MAX_LAYERS, enc.num_layers))
     noise = host.noise()
-    dev = src_tokens.device
-    bsz, seq_len = src_tokens.shape
+    dense = embeddings is not None
+    dev = embeddings.device if dense else src_tokens.device
+    bsz, seq_len = embeddings.shape[:2] if dense else src_tokens.shape
     lens_sorted, order_host = torch.sort(src_lengths.detach().to("cpu"), descending=True)     # on the host: no device sync per call
     # order, its inverse, the sorted lengths and the last-token index travel in ONE staging block (pinned: the copy does not make
     # the host wait for the stream), already in the int32 the kernels read
@@ -207,7 +252,8 @@ def encode(enc, style_ord, src_tokens, src_lengths, packed_index):
     H, E = enc.hidden_size, enc.embed_dim
 
     plan = _Plan()
-    plan.tokens = src_tokens.long().contiguous()         # (the kernels read int64; nn.Embedding also takes int32 ids)
+    plan.dense = dense
+    plan.tokens = None if dense else src_tokens.long().contiguous()   # (the kernels read int64; nn.Embedding also takes int32 ids)
     plan.order, plan.unsort, plan.lens, plan.last = on_dev[0], on_dev[1], on_dev[2], on_dev[3]
     plan.t_max, plan.layers, plan.padding_idx = int(lens_list[0]), enc.num_layers, enc.embed_tokens.padding_idx
     # The draws are those of the stock path, in its order and on its shapes: dropout_in on the embedded [seq_len,B,E] tokens, then per
@@ -236,4 +282,4 @@ def encode(enc, style_ord, src_tokens, src_lengths, packed_index):
     plan.owners_hh = [p["weight_hh"] for p in per_layer]
     plan.owners_b = [p["bias_ih"] + p["bias_hh"] for p in per_layer]
     params = [ops.cat_params(p[n], stack=True) for p in per_layer for n in names]
-    return _TxtStack.apply(plan, enc.embed_tokens.weight, style_ord, *params)
+    return _TxtStack.apply(plan, embeddings if dense else enc.embed_tokens.weight, style_ord, *params)

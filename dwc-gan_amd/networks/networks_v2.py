@@ -148,23 +148,56 @@ class TxtEncoder(nn.Module):
             # everything up to the heads' feature row on the kernels of csrc/txt_glue.hip: one launch per tensor built here
             return self._heads(txt.encode(self, style_ord, src_tokens, src_lengths, _packed_index))
         # DWC_TXT_FUSED=0: the same computation as stock tensor ops (the reference of tests/test_txt_fused.py)
-        noise = host.noise()
         tokens = src_tokens.transpose(1, 0)
-        seq_len, bsz = tokens.shape
+        return self._stock(style_ord, src_lengths, tokens.shape[0], tokens.shape[1], tokens.device,
+                           lambda order, lens_dev: self.embed_tokens(tokens.index_select(1, order)))
+
+    def forward_embed(self, style_ord, embeddings, lengths):
+        """``forward`` with the table lookup replaced by the caller's word vectors (reference networks_v2.py:256-293): ``embeddings``
+        [B, seq_len, embed_dim], ``lengths`` a tensor on any device or a list.  The reference takes lengths in decreasing order only;
+        any order is sorted here as ``forward`` does.  What lies behind a sample's length is never read (NaN and Inf included) and
+        its gradient is +0.0."""
+        if not torch.is_tensor(embeddings) or embeddings.dim() != 3:
+            raise ValueError("forward_embed: embeddings must be a [batch, seq_len, embed_dim] tensor, got %s"
+                             % (list(embeddings.shape) if torch.is_tensor(embeddings) else type(embeddings).__name__))
+        bsz, seq_len, width = embeddings.shape
+        if width != self.embed_dim:
+            raise ValueError("forward_embed: embeddings have width %d, the encoder's embed_dim is %d" % (width, self.embed_dim))
+        lens_host = (lengths.detach().to("cpu") if torch.is_tensor(lengths) else torch.as_tensor(lengths)).reshape(-1).long()
+        if lens_host.numel() != bsz:
+            raise ValueError("forward_embed: %d lengths for a batch of %d" % (lens_host.numel(), bsz))
+        if bsz < 1 or int(lens_host.min()) < 1 or int(lens_host.max()) > seq_len:
+            raise ValueError("forward_embed: every length must lie in 1..seq_len (%d), got %s" % (seq_len, lens_host.tolist()))
+        if not self.bidirectional:
+            raise NotImplementedError("the HIP text encoder is bidirectional (the reference's only configuration)")
+        if ops.TXT_FUSED and embeddings.is_cuda:
+            return self._heads(txt.encode(self, style_ord, None, lens_host, _packed_index, embeddings=embeddings.float().contiguous()))
+        # DWC_TXT_FUSED=0: the stock-tensor-op expression (the A/B partner of tests/test_txt_embed.py)
+        steps = torch.arange(seq_len, device=embeddings.device).view(-1, 1, 1)
+
+        def embed(order, lens_dev):
+            x = embeddings.float().transpose(0, 1).index_select(1, order)
+            return torch.where(steps < lens_dev.view(1, -1, 1), x, torch.zeros((), dtype=x.dtype, device=x.device))
+        return self._stock(style_ord, lens_host, seq_len, bsz, embeddings.device, embed)
+
+    def _stock(self, style_ord, src_lengths, seq_len, bsz, dev, embed):
+        """Everything of ``forward`` / ``forward_embed`` as stock tensor ops around ``ops.lstm_bidir``.  ``embed(order, lens_dev)``:
+        the embedded words [seq_len, B, E] in length-sorted order, before dropout_in."""
+        noise = host.noise()
         lens_host = src_lengths.detach().to("cpu")               # kept on the host: no device sync per call
         lens_sorted, order_host = torch.sort(lens_host, descending=True)
         # order, its inverse, the sorted lengths and the last-token index travel in ONE pinned staging block, asynchronously (r06: four
         # separate copies from pageable memory made the host wait for the stream four times per call -- with torch.normal's check that was
         # why the host could never run ahead of the GPU, benchmarks/host_vs_gpu.py)
-        if tokens.is_cuda and ops.PINNED_STAGE:
+        if dev.type == "cuda" and ops.PINNED_STAGE:
             stage = torch.empty(4, bsz, dtype=torch.int64).pin_memory()
             stage[0], stage[1], stage[2], stage[3] = order_host, torch.sort(order_host)[1], lens_sorted, lens_sorted - 1
-            on_dev = stage.to(tokens.device, non_blocking=True)
+            on_dev = stage.to(dev, non_blocking=True)
             order, unsort, lens_dev, last = on_dev[0], on_dev[1], on_dev[2].to(torch.int32), on_dev[3]
         else:
-            order, unsort = order_host.to(tokens.device), torch.sort(order_host)[1].to(tokens.device)
-            lens_dev, last = lens_sorted.to(torch.int32).to(tokens.device), (lens_sorted - 1).to(tokens.device)
-        emb = self.embed_tokens(tokens.index_select(1, order))
+            order, unsort = order_host.to(dev), torch.sort(order_host)[1].to(dev)
+            lens_dev, last = lens_sorted.to(torch.int32).to(dev), (lens_sorted - 1).to(dev)
+        emb = embed(order, lens_dev)
         emb = noise.dropout(emb, self.dropout_in, self.training)
         sty = _Permute.apply(style_ord, 0, order, unsort)
         # The packed bi-LSTM on the HIP recurrent kernels (hipdwc.ops.lstm_bidir): padded [T,B,*] tensors with per-sample
@@ -172,7 +205,7 @@ class TxtEncoder(nn.Module):
         lens_list = lens_sorted.tolist()
         t_max = int(lens_list[0])
         data = torch.cat([emb, sty.expand(seq_len, -1, -1)], -1)[:t_max]
-        cols = torch.arange(bsz, device=tokens.device)
+        cols = torch.arange(bsz, device=dev)
         suffixes = ("", "_reverse")
         hs, cs = [], []
         for l in range(self.num_layers):

@@ -924,6 +924,18 @@ int dwc_txt_operand_fwd(const float* table, const long long* tokens, const int* 
  * Each output may be NULL (a frozen table, a style that needs no gradient), not all three. */
 int dwc_txt_operand_bwd(const float* dxa, const float* dxb, const long long* tokens, const int* order, const float* mask,
                         float* d_cat, float* d_emb, long long* idx, int t_max, int B, int seq_len, int E, int S, void* stream);
+/* The layer-1 operand from the caller's embedded words instead of a table lookup (TxtEncoder.forward_embed; additive in ABI 11).
+ * emb:[B][seq_len][E] in CALLER order, lens:[B] the SORTED lengths (int32):
+ *   x[t][j] = [ t < lens[j] ? emb[order[j]][t] * mask[t][j] : 0 | style[order[j]] ]
+ * The zero is a select: what lies behind a sample's length is never loaded, so a NaN or Inf there reaches nothing.  On a table
+ * whose padding row is zero, x has the bits dwc_txt_operand_fwd writes for the matching tokens. */
+int dwc_txt_operand_embed_fwd(const float* emb, const int* order, const int* lens, const float* mask, const float* style, float* x,
+                              int t_max, int B, int seq_len, int E, int S, void* stream);
+/* Its adjoint.  d_emb:[B][seq_len][E] is the gradient of emb itself, in caller order, every element written once:
+ * (dxa + dxb)[t][j][:E] * mask[t][j] at row (order[j], t) where t < min(t_max, lens[j]), +0.0 elsewhere.  d_cat is what
+ * dwc_txt_operand_bwd writes.  Either output may be NULL, not both.  No scratch, no atomics. */
+int dwc_txt_operand_embed_bwd(const float* dxa, const float* dxb, const int* order, const int* lens, const float* mask, float* d_cat,
+                              float* d_emb, int t_max, int B, int seq_len, int E, int S, void* stream);
 /* The state entering each step, for the recurrent weight gradient of a layer: hprev[0][t] = out[0][t-1], hprev[1][t] = out[1][t+1],
  * zeros at t = 0 / t = T-1; out, hprev:[2][T][B][H].  One launch instead of a zero fill and two shifted copies. */
 int dwc_txt_prev_state(const float* out, float* hprev, int T, int B, int H, void* stream);
