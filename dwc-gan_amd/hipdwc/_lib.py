@@ -279,6 +279,11 @@ SIGNATURES = {
     # ---- the layer-1 operand from dense word embeddings (TxtEncoder.forward_embed; additive in ABI 11) ----
     "dwc_txt_operand_embed_fwd": (c_int, [c_fp] * 6 + [c_int] * 5 + [c_fp]),
     "dwc_txt_operand_embed_bwd": (c_int, [c_fp] * 7 + [c_int] * 5 + [c_fp]),
+    # ---- uint8 HWC crops to the internal image buffer (hipdwc.u8image; additive in ABI 11) ----
+    "dwc_image_u8_ksize": (c_int, [c_int, c_int]),
+    "dwc_image_u8_ws_bytes": (c_sz, [c_int] * 6),
+    "dwc_image_u8_to_nhwc4": (c_int, [c_fp] * 7 + [c_int] * 6 + [c_fp, c_sz, c_fp]),
+    "dwc_bf16_image_u8_to_nhwc8": (c_int, [c_fp] * 7 + [c_int] * 6 + [c_fp, c_sz, c_fp]),
 }
 
 ABI_VERSION = 11             # DWC_ABI_VERSION of include/dwcgan_hip.h

@@ -461,7 +461,8 @@ class Solver(nn.Module):
             if self.use_attention:
                 atts.append((heads[j - i:2 * (j - i), 3:4].float().expand(-1, 3, -1, -1) - 0.5) / 0.5)
         outs = torch.cat(outs, dim=1)
-        res = [x_real, outs[0], outs[1], outs[2]]
+        # (an internal image buffer, e.g. from hipdwc.u8image.image_from_u8, goes back as the fp32 NCHW image the writers take)
+        res = [x4[:, :3].float().contiguous() if ops.is_image(x_real) else x_real, outs[0], outs[1], outs[2]]
         if self.use_attention:
             res.append(torch.cat(atts))
         self.train()

@@ -961,6 +961,29 @@ int dwc_txt_states_fwd(dwc_txt_layers layers, const int* last, const int* unsort
 int dwc_txt_states_bwd(const float* d_feat, const int* order, const int* last, dwc_txt_layers grads, int T, int B, int H,
                        void* stream);
 
+/* ---- input pipeline: uint8 HWC crops to the internal image buffer (additive in ABI 11; csrc/image_u8.hip, DESIGN.md 25;
+ *      reference data_loader.py:11-22, the Resize / ToTensor / Normalize steps of its transform chain) -----------------------------
+ * One launch: PIL's antialiased BILINEAR resize of an 8-bit image (horizontal pass into an 8-bit intermediate, then the vertical
+ * pass, 22-bit fixed-point windows, 32-bit integer sums) and a table lookup, bit-equal to Image.resize + ToTensor + Normalize
+ * followed by dwc_pack_nchw_to_nhwc4 / dwc_pack_nchw_to_nhwc8_bf16.
+ *   u8:[B][Hin][Win][3] uint8, dense;  y:[B][Hout][Wout][4] fp32 or [B][Hout][Wout][8] bf16, every plane written (padding planes 0)
+ *   xstart:[Wout], xcoef:[Wout][kx], ystart:[Hout], ycoef:[Hout][ky] int32 on the device: output index i sums
+ *       v[start[i] + k] * coef[i][k], k < ksize, taps past the image's edge skipped; kx = dwc_image_u8_ksize(Win, Wout), ky likewise
+ *       (hipdwc/u8image.py resample_table builds them by PIL's rule); starts must not decrease.  Indices read from the windows are
+ *       clamped to the image, so a malformed table gives wrong pixels, never an access outside the buffers.
+ *   lut:[256] fp32: the value of each byte (the loader's ((b / 255) - 0.5) / 0.5); the bf16 form rounds it as the pack kernel does.
+ * C must be 3, every extent 1..16384, B <= 65535, and not Hin > 100 * Win with Hout < Hin (Image.resize takes such an image
+ * vertical pass first, which gives other bytes) -- else DWC_EINVAL, before any launch.  The 8-bit intermediate of a band of output
+ * rows lives in LDS; only where a single output row's source rows x Wout x 3 exceed 64 KiB it goes to `ws`, and
+ * dwc_image_u8_ws_bytes is non-zero (0 as well for a refused shape).  dwc_image_u8_ksize gives 0 for an extent outside 1..16384. */
+int dwc_image_u8_ksize(int n_in, int n_out);
+size_t dwc_image_u8_ws_bytes(int B, int Hin, int Win, int C, int Hout, int Wout);
+int dwc_image_u8_to_nhwc4(const uint8_t* u8, const int* xstart, const int* xcoef, const int* ystart, const int* ycoef, const float* lut,
+                          float* y, int B, int Hin, int Win, int C, int Hout, int Wout, void* ws, size_t ws_bytes, void* stream);
+int dwc_bf16_image_u8_to_nhwc8(const uint8_t* u8, const int* xstart, const int* xcoef, const int* ystart, const int* ycoef,
+                               const float* lut, void* y, int B, int Hin, int Win, int C, int Hout, int Wout, void* ws, size_t ws_bytes,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif
