@@ -18,7 +18,6 @@ files it writes:
   noise does to the reference itself, floored at one fp32 spacing of the key's largest value (what two fp32 recordings can resolve);
   the test's iteration-1 buffer tolerance is a multiple of it.
 """
-import json
 import os
 import sys
 
@@ -27,10 +26,9 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-import make_golden as mg  # noqa: E402  (import_reference, build_ref_solver, read_losses, t2n; synth)
+import tiny_record as tr  # noqa: E402  (the recording itself; make_golden's import_reference)
 
-synth = mg.synth
-t2n = mg.t2n
+t2n = tr.t2n
 
 # (name, B, Cin, Cout, H, k, stride, pad, activation) -- reflect padding; tests/test_batch_norm.py BN_CASES
 BN_CASES = [
@@ -44,7 +42,7 @@ BUF_REL = 1e-5         # the test's iteration-0 buffer tolerance (relative to th
 
 
 def tiny_bn_config():
-    cfg = synth.make_config(image_size=32, tiny=True)
+    cfg = tr.synth.make_config(image_size=32, tiny=True)
     cfg["dis"]["norm"] = "bn"
     return cfg
 
@@ -96,58 +94,32 @@ def gen_bn_ops(ref_nets):
             rec["y%d" % (j + 1)], rec["gy%d" % (j + 1)] = ys[j], gys[j]
         for kk, v in rec.items():
             out["%s/%s" % (name, kk)] = t2n(v)
-    np.savez_compressed(os.path.join(HERE, "bn_ops.npz"), **out)
+    tr.write("bn_ops", out, limit=False)
     print("bn_ops.npz:", len(out), "arrays")
 
 
-def run_tiny(ref_solver, cfg, batch, call_stats=None):
-    """Two iterations of the reference's tiny Solver with the BN-fed biases frozen -> (trainer after construction's init record,
-    flat record of losses / D gradients / buffers).  ``call_stats``: a list that receives, for every BN call of the FIRST dis_update,
-    (module name, batch mean, unbiased batch variance)."""
-    trainer = mg.build_ref_solver(ref_solver, cfg)
-    init = {"rng_state_after_init": torch.get_rng_state().numpy().copy()}
-    for k, v in trainer.gen.state_dict().items():
-        init["init/gen/%s" % k] = t2n(v)
-    for k, v in trainer.dis.state_dict().items():
-        init["init/dis/%s" % k] = t2n(v)
-    frozen = freeze_bn_fed_biases(trainer.dis)
-    out = {}
-    grabbed = {}
-    real_step = trainer.dis_opt.step
-
-    def grab_then_step(*args, **kw):
-        for k, p in trainer.dis.named_parameters():
-            if p.grad is not None:
-                grabbed[k] = t2n(p.grad)
-        return real_step(*args, **kw)
-    trainer.dis_opt.step = grab_then_step
+def record_bn(ref_solver, cfg, batch, call_stats=None):
+    """The shared two-iteration recording with the BN-fed biases frozen and every BN buffer recorded after each dis_update and
+    gen_update.  ``call_stats``: a list that receives, for every BN call of the FIRST dis_update, (module name, batch mean,
+    unbiased batch variance)."""
     hooks = []
-    if call_stats is not None:
-        for n, m in bn_modules(trainer.dis):
-            hooks.append(m.register_forward_pre_hook(
-                lambda mod, inp, n=n: call_stats.append((n, inp[0].detach().double().mean((0, 2, 3)),
-                                                         inp[0].detach().double().var((0, 2, 3), unbiased=True)))))
-    losses = []
-    for it in range(2):
-        a = (batch["x_real"], batch["c_src"], batch["c_trg"], batch["txt"], batch["txt_lens"], batch["label_src"],
-             batch["label_trg"], cfg, it)
-        grabbed.clear()
-        trainer.dis_update(*a)
-        for h in hooks:
-            h.remove()
-        hooks = []
-        for k, v in grabbed.items():
-            out["it%d/dgrad/%s" % (it, k)] = v
-        for k, v in bn_state(trainer).items():
-            out["it%d/after_dis/%s" % (it, k)] = t2n(v)
-        trainer.gen_update(*a)
-        for k, v in bn_state(trainer).items():
-            out["it%d/after_gen/%s" % (it, k)] = t2n(v)
-        trainer.smooth_moving()
-        trainer.update_learning_rate()
-        trainer.update_attention_status(it)
-        losses.append(mg.read_losses(trainer))
-    return init, out, losses, frozen
+
+    def watch_calls(it, trainer):
+        if it == 0 and call_stats is not None:
+            for n, m in bn_modules(trainer.dis):
+                hooks.append(m.register_forward_pre_hook(
+                    lambda mod, inp, n=n: call_stats.append((n, inp[0].detach().double().mean((0, 2, 3)),
+                                                             inp[0].detach().double().var((0, 2, 3), unbiased=True)))))
+
+    def buffers(when):
+        def record(it, trainer, out):
+            while hooks:
+                hooks.pop().remove()
+            for k, v in bn_state(trainer).items():
+                out["it%d/after_%s/%s" % (it, when, k)] = t2n(v)
+        return record
+    return tr.two_iterations(ref_solver, cfg, batch, full_init=True, freeze=freeze_bn_fed_biases, before_dis=watch_calls,
+                             after_dis=buffers("dis"), after_gen=buffers("gen"), g_samples=False)
 
 
 def replay(r0_mean, r0_var, stats, order):
@@ -160,33 +132,17 @@ def replay(r0_mean, r0_var, stats, order):
 
 def gen_tiny_bn(ref_solver):
     cfg = tiny_bn_config()
-    B = 3
-    batch = synth.make_batch(B, 32, seed=4321)
+    batch = tr.tiny_batch()
     calls = []
-    init, rec, losses, frozen = run_tiny(ref_solver, cfg, batch, calls)
-    np.savez_compressed(os.path.join(HERE, "tiny_bn_init.npz"), **init)     # (a file of its own: each stays under 1 MiB)
-    out = {"rng_state_after_init": init["rng_state_after_init"]}
-    for k, v in batch.items():
-        out["batch/%s" % k] = t2n(v)
-    out.update(rec)
-    out["losses_json"] = np.frombuffer(json.dumps(losses).encode(), dtype=np.uint8)
-    out["frozen_json"] = np.frombuffer(json.dumps(frozen).encode(), dtype=np.uint8)
+    init, rec, losses, frozen = record_bn(ref_solver, cfg, batch, calls)
+    tr.write("tiny_bn_init", init, limit=False)     # (a file of its own: each stays under 1 MiB)
+    out = tr.assemble({"rng_state_after_init": init["rng_state_after_init"]}, batch, rec, losses, frozen)
 
     # what one ulp of input noise does to the reference itself
-    g = torch.Generator().manual_seed(5)
-    noisy = dict(batch)
-    noisy["x_real"] = batch["x_real"] * (1 + 2.0 ** -23 * torch.randn(batch["x_real"].shape, generator=g))
-    _, rec2, losses2, _ = run_tiny(ref_solver, cfg, noisy)
-    worst = {}
-    for k, v in rec.items():
-        d = float(np.abs(v.astype(np.float64) - rec2[k].astype(np.float64)).max())
-        if v.dtype == np.float32:
-            # two fp32 recordings cannot show a deviation below the spacing of the values themselves (0 here means "under one
-            # ulp", not "insensitive"): floored at one fp32 spacing of the key's largest magnitude
-            d = max(d, float(np.spacing(np.float32(np.abs(v).max()))))
-        out["sens/%s" % k] = np.float64(d)
-        kind = k.split("/")[0] + "/" + k.split("/")[1]
-        worst[kind] = max(worst.get(kind, 0.0), d)
+    _, rec2, losses2, _ = record_bn(ref_solver, cfg, tr.one_ulp(batch))
+    sens, worst = tr.sensitivity(rec, rec2, losses, losses2)
+    for k in rec:
+        out["sens/%s" % k] = np.float64(sens[k])
     for it in range(2):
         out["sens/it%d/losses" % it] = np.float64(max(abs(losses[it][k] - losses2[it][k]) for k in losses[it]))
     print("sensitivity (largest deviation per kind):", {k: "%.2e" % v for k, v in sorted(worst.items())},
@@ -212,11 +168,11 @@ def gen_tiny_bn(ref_solver):
             ratio = max(float((rm - want_m).abs().max()) / tol_m, float((rv - want_v).abs().max()) / tol_v)
             print("%s: order %s is off by %.0f x the tolerance" % (n, wrong, ratio))
             assert ratio >= 100, (n, wrong, ratio)
-    np.savez_compressed(os.path.join(HERE, "tiny_bn_step.npz"), **out)
+    tr.write("tiny_bn_step", out, limit=False)
     print("tiny_bn_step.npz written; frozen:", frozen, "losses:", [(l["loss_dis_all"], l["loss_gen_total"]) for l in losses])
 
 
 if __name__ == "__main__":
-    ref_solver, ref_nets, _, _, _ = mg.import_reference()
+    ref_solver, ref_nets, _, _, _ = tr.mg.import_reference()
     gen_bn_ops(ref_nets)
     gen_tiny_bn(ref_solver)

@@ -33,27 +33,19 @@ handled the way make_golden_lrelu.py handles the biases in front of an instance 
   ``sens`` of these keys is therefore floored at one fp32 spacing of sum_i |d loss / d src_i| of that D step and scale (measured with
   hooks on the reference's src maps; 2.0 -> 2.4e-7), the same rule -- one spacing of what was rounded -- applied to the summands.
 """
-import json
 import os
 import sys
 
 import numpy as np
-import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-import make_golden as mg  # noqa: E402  (import_reference, build_ref_solver, read_losses, checksum, t2n; synth)
-from make_golden_lrelu import sample_idx  # noqa: E402  (which entries of a G gradient the fixtures keep)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import tiny_record as tr  # noqa: E402  (the recording itself; make_golden's import_reference)
 
-synth = mg.synth
-t2n = mg.t2n
-BATCH_SEED = 4321
 MAX_SRC = 6.0
-LIMIT_BYTES = 290030          # tiny_bn_step.npz
 
 
 def tiny_gan_config(gan_type, gp_w):
-    cfg = synth.make_config(image_size=32, tiny=True)
+    cfg = tr.synth.make_config(image_size=32, tiny=True)
     cfg["dis"]["gan_type"] = gan_type
     cfg["gp_w"] = gp_w
     return cfg
@@ -92,102 +84,36 @@ def freeze_src_biases(dis):
     return frozen
 
 
-def run_tiny(ref_solver, cfg, batch, probe):
-    """make_golden_lrelu.py run_tiny, with the src biases frozen for wgan and the probe read after each D step."""
-    trainer = mg.build_ref_solver(ref_solver, cfg)
-    init = {"rng_state_after_init": torch.get_rng_state().numpy().copy()}
-    for net, mod in (("gen", trainer.gen), ("dis", trainer.dis)):
-        sd = mod.state_dict()
-        init["init_keys/%s" % net] = np.frombuffer(json.dumps([[k, list(v.shape)] for k, v in sd.items()]).encode(), dtype=np.uint8)
-        init["init_sums/%s" % net] = np.array([mg.checksum(v) for v in sd.values()], dtype=np.float64)
-    frozen = freeze_src_biases(trainer.dis) if cfg["dis"]["gan_type"] == "wgan" else []
-    out, grabbed, src_terms = {}, {}, {}
-    real_step = trainer.dis_opt.step
+def run_probed(ref_solver, cfg, batch, probe):
+    """The shared two-iteration recording with the src biases frozen for wgan and the probe read after each D step
+    -> (what tr.two_iterations returns, key of a src bias' gradient -> sum |d loss / d src_i| of that D step and scale)."""
+    src_terms = {}
 
-    def grab_then_step(*args, **kw):
-        for k, p in trainer.dis.named_parameters():
-            if p.grad is not None:
-                grabbed[k] = t2n(p.grad)
-        return real_step(*args, **kw)
-    trainer.dis_opt.step = grab_then_step
-    losses, gnames, gsamples, gstats = [], [], [], []
-    for it in range(2):
-        a = (batch["x_real"], batch["c_src"], batch["c_trg"], batch["txt"], batch["txt_lens"], batch["label_src"],
-             batch["label_trg"], cfg, it)
-        grabbed.clear()
-        probe.abs_grad.clear()
-        trainer.dis_update(*a)
+    def read_probe(it, trainer, out):
         for scale, v in probe.abs_grad.items():
-            src_terms["it%d/dgrad/cnns_src.%d.bias" % (it, scale)] = v
-        for k, v in grabbed.items():
-            out["it%d/dgrad/%s" % (it, k)] = v
-        trainer.gen_update(*a)
-        for k, p in trainer.gen.named_parameters():
-            if it == 0 and p.grad is not None:
-                flat = p.grad.detach().reshape(-1)
-                d = flat.double()
-                gnames.append(k)
-                gsamples.append(t2n(flat[torch.from_numpy(sample_idx(flat.numel()))]))
-                gstats.append([float(d.abs().max()), float(d.sum()), float((d * d).sum())])
-        trainer.smooth_moving()
-        trainer.update_learning_rate()
-        trainer.update_attention_status(it)
-        losses.append(mg.read_losses(trainer))
-    out["it0/ggrad"] = np.concatenate(gsamples)
-    out["it0/gstat"] = np.array(gstats, dtype=np.float64)
-    init["it0/ggrad_names"] = np.frombuffer(json.dumps(gnames).encode(), dtype=np.uint8)
-    return init, out, losses, frozen, src_terms
+            src_terms[(tr.ts.DGRAD % it) + "cnns_src.%d.bias" % scale] = v
+    run = tr.two_iterations(ref_solver, cfg, batch, freeze=freeze_src_biases if cfg["dis"]["gan_type"] == "wgan" else None,
+                            before_dis=lambda it, trainer: probe.abs_grad.clear(), after_dis=read_probe)
+    return run, src_terms
 
 
 def gen_variant(ref_solver, ref_nets, name, gan_type, gp_w):
     cfg = tiny_gan_config(gan_type, gp_w)
-    batch = synth.make_batch(3, 32, seed=BATCH_SEED)
+    batch = tr.tiny_batch()
     with DisProbe(ref_nets) as probe:
-        init, rec, losses, frozen, src_terms = run_tiny(ref_solver, cfg, batch, probe)
+        first, src_terms = run_probed(ref_solver, cfg, batch, probe)
         worst_src = probe.worst
         assert worst_src > 0.0 and len(src_terms) == 4, (worst_src, src_terms)
         if gan_type == "nsgan":
             assert worst_src < MAX_SRC, "nsgan: the reference's D reached |src| = %.3f >= %g: choose another batch seed" % (worst_src, MAX_SRC)
-        # what one ulp of input noise does to the reference itself
-        g = torch.Generator().manual_seed(5)
-        noisy = dict(batch)
-        noisy["x_real"] = batch["x_real"] * (1 + 2.0 ** -23 * torch.randn(batch["x_real"].shape, generator=g))
-        _, rec2, losses2, _, _ = run_tiny(ref_solver, cfg, noisy, probe)
-    out = dict(init)
-    for k, v in batch.items():
-        out["batch/%s" % k] = t2n(v)
-    out.update(rec)
-    out["losses_json"] = np.frombuffer(json.dumps(losses).encode(), dtype=np.uint8)
-    out["frozen_json"] = np.frombuffer(json.dumps(frozen).encode(), dtype=np.uint8)
-    out["max_abs_src"] = np.array(worst_src, dtype=np.float64)
-    worst, sens = {}, {}
-    for k, v in rec.items():
-        if k == "it0/gstat":
-            continue
-        a, b = v.astype(np.float64), rec2[k].astype(np.float64)
-        d = max(float(np.abs(a - b).max()), float(np.spacing(np.float32(np.abs(a).max()))))
-        if k in src_terms:          # a cancelling sum: one spacing of the summands' total magnitude (module docstring)
-            d = max(d, float(np.spacing(np.float32(src_terms[k]))))
-        sens[k] = d
-        kind = "/".join(k.split("/")[:2])
-        worst[kind] = max(worst.get(kind, 0.0), d)
-    for it in range(2):
-        for k in losses[it]:
-            d = abs(losses[it][k] - losses2[it][k])
-            sens["it%d/loss/%s" % (it, k)] = max(d, float(np.spacing(np.float32(abs(losses[it][k])))))
-    out["sens_json"] = np.frombuffer(json.dumps(sens).encode(), dtype=np.uint8)
-    print("%s: largest |src| %.3e; sum |d loss / d src| per D step and scale %s; sensitivity (largest deviation per kind):"
-          % (name, worst_src, {k: "%.4g" % v for k, v in sorted(src_terms.items())}), {k: "%.2e" % v for k, v in sorted(worst.items())},
-          "losses", ["%.2e" % max(sens["it%d/loss/%s" % (it, k)] for k in losses[it]) for it in range(2)])
-    path = os.path.join(HERE, "%s.npz" % name)
-    np.savez_compressed(path, **out)
-    size = os.path.getsize(path)
-    assert size < LIMIT_BYTES, (path, size)
-    print("%s written (%d bytes); frozen: %s; losses: %s" % (os.path.basename(path), size, frozen,
-                                                              [(l["loss_dis_all"], l["loss_gen_adv"], l["loss_gen_total"]) for l in losses]))
+        second, _ = run_probed(ref_solver, cfg, tr.one_ulp(batch), probe)
+    print("%s: largest |src| %.3e; sum |d loss / d src| per D step and scale %s"
+          % (name, worst_src, {k: "%.4g" % v for k, v in sorted(src_terms.items())}))
+    # (a src bias' gradient is a cancelling sum: its sens is floored at one spacing of the summands' total magnitude, module docstring)
+    tr.write_with_sens(name, name, batch, first, second, floors=src_terms, extra={"max_abs_src": np.array(worst_src, dtype=np.float64)})
 
 
 if __name__ == "__main__":
-    ref = mg.import_reference()
+    ref = tr.mg.import_reference()
     gen_variant(ref[0], ref[1], "tiny_nsgan", "nsgan", 0)
     gen_variant(ref[0], ref[1], "tiny_wgan_gp", "wgan", 10)

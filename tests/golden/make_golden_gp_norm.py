@@ -18,51 +18,32 @@ bias in front of an instance norm: the reference records rounding noise there) i
 script asserts every sensitivity below a QUARTER of that bound and walks BATCH_SEEDS until one holds; ``meta`` records the seed
 (the tests build the batch from it).  Both variants hold at the first, 4321.  Each file stays below tiny_bn_step.npz.
 """
-import json
 import os
 import sys
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-import make_golden as mg  # noqa: E402  (import_reference, build_ref_solver, t2n; synth)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import tiny_record as tr  # noqa: E402  (the recording itself; make_golden's import_reference)
 
-synth = mg.synth
 BATCH_SEEDS = (4321, 4322, 4323, 4324)
-LIMIT_BYTES = 290030          # tiny_bn_step.npz
-SCALARS = ("loss_dis", "loss_dis_all", "loss_gp", "loss_r1")
+SCALARS = tr.PENALTY_SCALARS
 
 
 def run(ref_solver, norm, x_scale, batch_seed):
-    cfg = synth.make_config(image_size=32, tiny=True)
+    cfg = tr.synth.make_config(image_size=32, tiny=True)
     cfg["dis"]["norm"] = norm
     cfg["gp_w"], cfg["use_r1"] = 10.0, True
-    trainer = mg.build_ref_solver(ref_solver, cfg)
-    out = {"rng_state_after_init": torch.get_rng_state().numpy().copy()}
-    batch = synth.make_batch(3, 32, seed=batch_seed)
-    grabbed = {}
-    real_step = trainer.dis_opt.step
 
-    def grab_then_step(*args, **kw):
-        for k, p in trainer.dis.named_parameters():
-            grabbed["grad/" + k] = mg.t2n(p.grad)
-        return real_step(*args, **kw)
-    trainer.dis_opt.step = grab_then_step
-    real_gp = trainer.gradient_penalty
+    def keep_x_hat(trainer, out):
+        real_gp = trainer.gradient_penalty
 
-    def gp_and_its_input(y, x):
-        out["x_hat"] = mg.t2n(x)                       # (alpha and x_fake come from the recording's random stream and generator)
-        return real_gp(y, x)
-    trainer.gradient_penalty = gp_and_its_input
-    x_real = batch["x_real"].clone() * x_scale        # (the reference sets requires_grad on the tensor it is handed)
-    trainer.dis_update(x_real, batch["c_src"], batch["c_trg"], batch["txt"], batch["txt_lens"], batch["label_src"],
-                       batch["label_trg"], cfg, 15)
-    out.update(grabbed)
-    for k in SCALARS:
-        out[k] = np.float64(float(getattr(trainer, k)))
-    return out
+        def gp_and_its_input(y, x):
+            out["x_hat"] = tr.t2n(x)                   # (alpha and x_fake come from the recording's random stream and generator)
+            return real_gp(y, x)
+        trainer.gradient_penalty = gp_and_its_input
+    return tr.penalties(ref_solver, cfg, tr.tiny_batch(batch_seed), x_scale=x_scale, setup=keep_x_hat)[1]
 
 
 def bound(rec, k, norm):
@@ -83,8 +64,7 @@ def gen_variant(ref_solver, norm):
         for k in rec:
             if k in ("rng_state_after_init", "x_hat"):
                 continue
-            a, b = np.asarray(rec[k], dtype=np.float64), np.asarray(rec2[k], dtype=np.float64)
-            sens[k] = max(float(np.abs(a - b).max()), float(np.spacing(np.float32(np.abs(a).max()))))
+            sens[k] = tr.deviation(rec[k], rec2[k])
             lim = bound(rec, k, norm)
             worst = max(worst, sens[k] / lim if lim > 0 else 0.0)
         print("norm %s, batch seed %d: largest sensitivity / bound %.3f" % (norm, seed, worst))
@@ -92,17 +72,14 @@ def gen_variant(ref_solver, norm):
             break
     else:
         raise SystemExit("norm %s: no batch seed of %s keeps every sensitivity below a quarter of its bound" % (norm, BATCH_SEEDS))
-    rec["sens_json"] = np.frombuffer(json.dumps(sens).encode(), dtype=np.uint8)
-    rec["meta"] = np.frombuffer(json.dumps({"gp_w": 10.0, "use_r1": True, "iters": 15, "B": 3, "S": 32, "batch_seed": seed,
-                                            "seed": 1234, "norm": norm}).encode(), dtype=np.uint8)
-    path = os.path.join(HERE, "tiny_penalties_%s.npz" % norm)
-    np.savez_compressed(path, **rec)
-    size = os.path.getsize(path)
-    assert size < LIMIT_BYTES, (path, size)
-    print("%s written (%d bytes):" % (os.path.basename(path), size), {k: float(rec[k]) for k in SCALARS})
+    rec["sens_json"] = tr.json_bytes(sens)
+    rec["meta"] = tr.json_bytes({"gp_w": 10.0, "use_r1": True, "iters": 15, "B": 3, "S": 32, "batch_seed": seed, "seed": 1234,
+                                 "norm": norm})
+    size = tr.write("tiny_penalties_%s" % norm, rec)
+    print("tiny_penalties_%s.npz written (%d bytes):" % (norm, size), {k: float(rec[k]) for k in SCALARS})
 
 
 if __name__ == "__main__":
-    ref = mg.import_reference()
+    ref = tr.mg.import_reference()
     for norm in ("ln", "in"):
         gen_variant(ref[0], norm)

@@ -13,19 +13,15 @@ files it writes:
 * tiny_sn_step.npz -- the same Solver: two iterations with every loss scalar, every D gradient of each D step and every SN u / v after each dis_update
   and gen_update; one more D step from the same initialisation with gp_w = 10 and use_r1 (iteration 15).
 """
-import json
 import os
 import sys
 
-import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-import make_golden as mg  # noqa: E402  (import_reference, build_ref_solver, read_losses, t2n; synth)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import tiny_record as tr  # noqa: E402  (the recording itself; make_golden's import_reference)
 
-synth = mg.synth
-t2n = mg.t2n
+t2n = tr.t2n
 
 # (name, B, Cin, Cout, H, k, stride, pad, activation) -- reflect padding; tests/test_spectral_norm.py SN_CASES
 SN_CASES = [
@@ -37,7 +33,7 @@ SN_CASES = [
 
 
 def tiny_sn_config():
-    cfg = synth.make_config(image_size=32, tiny=True)
+    cfg = tr.synth.make_config(image_size=32, tiny=True)
     cfg["dis"]["norm"] = "sn"
     return cfg
 
@@ -64,78 +60,34 @@ def gen_sn_ops(ref_nets):
         rec.update({"x": x, "y1": ys[0], "y3": ys[2], "gy": gy, "dx": x.grad, "dw": m.weight_bar.grad, "db": m.bias.grad})
         for kk, v in rec.items():
             out["%s/%s" % (name, kk)] = t2n(v)
-    np.savez_compressed(os.path.join(HERE, "sn_ops.npz"), **out)
+    tr.write("sn_ops", out, limit=False)
     print("sn_ops.npz:", len(out), "arrays")
+
+
+def record_uv(trainer, out, prefix):
+    for k, v in sn_state(trainer).items():
+        out[prefix + k] = t2n(v)
 
 
 def gen_tiny_sn(ref_solver):
     cfg = tiny_sn_config()
-    B = 3
-    trainer = mg.build_ref_solver(ref_solver, cfg)
-    init = {"rng_state_after_init": torch.get_rng_state().numpy().copy()}
-    for k, v in trainer.gen.state_dict().items():
-        init["init/gen/%s" % k] = t2n(v)
-    for k, v in trainer.dis.state_dict().items():
-        init["init/dis/%s" % k] = t2n(v)
-    np.savez_compressed(os.path.join(HERE, "tiny_sn_init.npz"), **init)     # (a file of its own: each stays under 1 MiB)
-    out = {"rng_state_after_init": init["rng_state_after_init"]}
-    batch = synth.make_batch(B, 32, seed=4321)
-    for k, v in batch.items():
-        out["batch/%s" % k] = t2n(v)
-    grabbed = {}
-    real_step = trainer.dis_opt.step
-
-    def grab_then_step(*args, **kw):
-        for k, p in trainer.dis.named_parameters():
-            if p.grad is not None:
-                grabbed[k] = t2n(p.grad)
-        return real_step(*args, **kw)
-    trainer.dis_opt.step = grab_then_step
-    losses = []
-    for it in range(2):
-        a = (batch["x_real"], batch["c_src"], batch["c_trg"], batch["txt"], batch["txt_lens"], batch["label_src"],
-             batch["label_trg"], cfg, it)
-        grabbed.clear()
-        trainer.dis_update(*a)
-        for k, v in grabbed.items():
-            out["it%d/dgrad/%s" % (it, k)] = v
-        for k, v in sn_state(trainer).items():
-            out["it%d/after_dis/%s" % (it, k)] = t2n(v)
-        trainer.gen_update(*a)
-        for k, v in sn_state(trainer).items():
-            out["it%d/after_gen/%s" % (it, k)] = t2n(v)
-        trainer.smooth_moving()
-        trainer.update_learning_rate()
-        trainer.update_attention_status(it)
-        losses.append(mg.read_losses(trainer))
-    out["losses_json"] = np.frombuffer(json.dumps(losses).encode(), dtype=np.uint8)
+    batch = tr.tiny_batch()
+    init, rec, losses, _ = tr.two_iterations(ref_solver, cfg, batch, full_init=True, g_samples=False,
+                                             after_dis=lambda it, trainer, out: record_uv(trainer, out, "it%d/after_dis/" % it),
+                                             after_gen=lambda it, trainer, out: record_uv(trainer, out, "it%d/after_gen/" % it))
+    tr.write("tiny_sn_init", init, limit=False)     # (a file of its own: each stays under 1 MiB)
+    out = tr.assemble({"rng_state_after_init": init["rng_state_after_init"]}, batch, rec, losses)
 
     # gradient penalty + R1 (reference solver.py:337-350) on one D step from the same initialisation, iteration 15
-    cfg_p = dict(cfg, gp_w=10.0, use_r1=True)
-    trainer = mg.build_ref_solver(ref_solver, cfg_p)
-    real_step = trainer.dis_opt.step
-    grabbed = {}
-
-    def grab_then_step_p(*args, **kw):
-        for k, p in trainer.dis.named_parameters():
-            if p.grad is not None:
-                grabbed[k] = t2n(p.grad)
-        return real_step(*args, **kw)
-    trainer.dis_opt.step = grab_then_step_p
-    x_real = batch["x_real"].clone()                  # (the reference sets requires_grad on the tensor it is handed)
-    trainer.dis_update(x_real, batch["c_src"], batch["c_trg"], batch["txt"], batch["txt_lens"], batch["label_src"],
-                       batch["label_trg"], cfg_p, 15)
-    for k, v in grabbed.items():
-        out["pen/dgrad/%s" % k] = v
-    for k in ("loss_dis", "loss_dis_all", "loss_gp", "loss_r1"):
-        out["pen/%s" % k] = np.float64(float(getattr(trainer, k)))
-    for k, v in sn_state(trainer).items():
-        out["pen/after_dis/%s" % k] = t2n(v)
-    np.savez_compressed(os.path.join(HERE, "tiny_sn_step.npz"), **out)
+    trainer, pen = tr.penalties(ref_solver, dict(cfg, gp_w=10.0, use_r1=True), batch, grad_prefix="pen/dgrad/", scalar_prefix="pen/")
+    del pen["rng_state_after_init"]
+    out.update(pen)
+    record_uv(trainer, out, "pen/after_dis/")
+    tr.write("tiny_sn_step", out, limit=False)
     print("tiny_sn_step.npz written; losses:", [(l["loss_dis_all"], l["loss_gen_total"]) for l in losses])
 
 
 if __name__ == "__main__":
-    ref_solver, ref_nets, _, _, _ = mg.import_reference()
+    ref_solver, ref_nets, _, _, _ = tr.mg.import_reference()
     gen_sn_ops(ref_nets)
     gen_tiny_sn(ref_solver)

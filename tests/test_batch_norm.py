@@ -9,7 +9,6 @@ given order, eval mode, one segmented call = S single calls bit for bit, run-to-
 reference, buffers included."""
 import ctypes
 import functools
-import json
 import os
 import re
 
@@ -19,7 +18,8 @@ import torch
 import torch.nn.functional as F
 
 import guarded_alloc as ga
-from hipdwc import _lib, batchnorm, host, ops, synth
+import tiny_solver as ts
+from hipdwc import _lib, batchnorm, ops, synth
 
 T = torch.from_numpy
 DEV = "cuda:0"
@@ -67,16 +67,6 @@ def _bn_config():
     return cfg
 
 
-def _build(cfg, device="cpu"):
-    from solver import Solver
-    torch.manual_seed(1234)
-    s = Solver(cfg, torch.device(device), None)
-    if device != "cpu":
-        s = s.to(device)
-    s.copy_nets()
-    return s
-
-
 def _act(y, act):
     return {"none": lambda t: t, "relu": torch.relu, "lrelu": lambda t: F.leaky_relu(t, 0.1), "tanh": torch.tanh}[act](y)
 
@@ -110,7 +100,7 @@ def test_bn_symbols_header_table_library():
 def test_tiny_bn_init_equals_reference(golden_dir):
     import networks.networks as nets
     ref = np.load(os.path.join(golden_dir, "tiny_bn_init.npz"))
-    s = _build(_bn_config())
+    s = ts.build(_bn_config())
     for prefix, mod in (("init/gen/", s.gen), ("init/dis/", s.dis)):
         sd = mod.state_dict()
         want = {k[len(prefix):]: ref[k] for k in ref.files if k.startswith(prefix)}
@@ -128,7 +118,7 @@ def test_tiny_bn_init_equals_reference(golden_dir):
     in_opt = {id(p) for p in s.dis_opt.param_groups[0]["params"]}
     assert all(id(m.weight) in in_opt and id(m.bias) in in_opt for m in bns)
     # a reference checkpoint loads strictly
-    fresh = _build(_bn_config())
+    fresh = ts.build(_bn_config())
     fresh.dis.load_state_dict({k[len("init/dis/"):]: T(ref[k]) for k in ref.files if k.startswith("init/dis/")}, strict=True)
 
 
@@ -602,74 +592,35 @@ def _buffers(s):
             if k.endswith("running_mean") or k.endswith("running_var") or k.endswith("num_batches_tracked")}
 
 
-def _grab_dis(s):
-    grabbed = {}
-    real_step = s.dis_opt.step
-
-    def grab(*a, **k):
-        grabbed.update({n: (None if p.grad is None else p.grad.detach().clone()) for n, p in s.dis.named_parameters()})
-        return real_step(*a, **k)
-    s.dis_opt.step = grab
-    return grabbed
-
-
 @pytest.mark.gpu
 def test_tiny_bn_two_iterations_vs_reference(golden_dir):
     """dis.norm 'bn': two iterations of the tiny Solver (HostNoise, the reference's random stream) against the imported reference
     (its BN-fed convolution biases frozen: tests/golden/make_golden_bn.py): every loss scalar, every D gradient the fixture holds of
-    both D steps, every BN buffer after each dis_update (four updates per layer, order fake, real, fake1, real) and each gen_update
-    (two more).  Iteration-1 buffers: 16 x the deviation the reference itself shows under one ulp of input noise (``sens``)."""
-    ref = np.load(os.path.join(golden_dir, "tiny_bn_step.npz"))
-    want = json.loads(bytes(ref["losses_json"]).decode())
-    frozen = set(json.loads(bytes(ref["frozen_json"]).decode()))
-    host.set_noise(host.HostNoise())
-    try:
-        cfg = _bn_config()
-        s = _build(cfg, DEV)
-        assert torch.equal(torch.get_rng_state(), T(ref["rng_state_after_init"]))
-        batch = {k[len("batch/"):]: T(ref[k]).to(DEV) for k in ref.files if k.startswith("batch/")}
-        grabbed = _grab_dis(s)
+    both D steps (a frozen bias: none, or exact zeros), every BN buffer after each dis_update (four updates per layer, order fake,
+    real, fake1, real) and each gen_update (two more).  Iteration-1 buffers: 16 x the deviation the reference itself shows under
+    one ulp of input noise (``sens``)."""
+    fx = ts.load(golden_dir, "tiny_bn_step")
+    ref = fx.npz
 
-        def check_buffers(it, when):
-            for k, v in _buffers(s).items():
-                key = "it%d/after_%s/%s" % (it, when, k)
-                w = T(ref[key])
-                if k.endswith("num_batches_tracked"):
-                    assert int(v) == int(w) == 6 * it + (4 if when == "dis" else 6), (key, int(v), int(w))
-                    continue
-                err = (v.detach().cpu().double() - w.double()).abs().max().item()
-                lim = 1e-5 * w.abs().max().item() if it == 0 else 16 * float(ref["sens/" + key])
-                print("%s: max err %.3e, limit %.3e, ratio to sens %.1f" % (key, err, lim, err / max(float(ref["sens/" + key]), 1e-30)))
-                assert err <= lim, "%s: max err %.3e > %.3e" % (key, err, lim)
+    def check_buffers(it, s, when):
+        for k, v in _buffers(s).items():
+            key = "it%d/after_%s/%s" % (it, when, k)
+            w = T(ref[key])
+            if k.endswith("num_batches_tracked"):
+                assert int(v) == int(w) == 6 * it + (4 if when == "dis" else 6), (key, int(v), int(w))
+                continue
+            err = (v.detach().cpu().double() - w.double()).abs().max().item()
+            lim = 1e-5 * w.abs().max().item() if it == 0 else 16 * float(ref["sens/" + key])
+            print("%s: max err %.3e, limit %.3e, ratio to sens %.1f" % (key, err, lim, err / max(float(ref["sens/" + key]), 1e-30)))
+            assert err <= lim, "%s: max err %.3e > %.3e" % (key, err, lim)
 
-        for it in range(2):
-            a = (batch["x_real"], batch["c_src"], batch["c_trg"], batch["txt"], batch["txt_lens"], batch["label_src"],
-                 batch["label_trg"], cfg, it)
-            grabbed.clear()
-            s.dis_update(*a)
-            check_buffers(it, "dis")
-            ref_g = {k[len("it%d/dgrad/" % it):]: T(ref[k]) for k in ref.files if k.startswith("it%d/dgrad/" % it)}
-            assert set(ref_g) | frozen == set(grabbed) and not set(ref_g) & frozen
-            for k in frozen:                              # d/d bias in front of a training-mode batch norm: none, or exact zeros
-                assert grabbed[k] is None or not grabbed[k].any(), k
-            for k, g in ref_g.items():
-                close(grabbed[k], g, rel=2e-3 if it == 0 else 2e-2, msg="it%d dgrad %s" % (it, k))
-            s.gen_update(*a)
-            check_buffers(it, "gen")
-            s.smooth_moving()
-            s.update_learning_rate()
-            s.update_attention_status(it)
-            tol = (2e-4, 5e-3)[it]
-            for k, v in want[it].items():
-                got = float(torch.as_tensor(getattr(s, k)).detach())
-                assert abs(got - v) <= tol * max(1.0, abs(v)), (it, k, got, v)
-    finally:
-        host.set_noise(host.DeviceNoise())
+    ts.two_iterations(fx, _bn_config(), ts.FIXED_BOUNDS, init=False,          # (tiny_bn_init.npz holds the initial tensors themselves)
+                      after_dis=lambda it, s: check_buffers(it, s, "dis"), after_gen=lambda it, s: check_buffers(it, s, "gen"))
 
 
 @pytest.mark.gpu
 def test_bn_penalties_stay_unbuilt():
-    s = _build(_bn_config(), DEV)
+    s = ts.build(_bn_config(), DEV)
     assert not s.dis.penalty_hip_ok()
     with pytest.raises(NotImplementedError):
         s.dis.forward_src_scale0_torch(torch.randn(2, 3, 32, 32, device=DEV))

@@ -19,6 +19,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import tiny_solver as ts                                    # noqa: E402
 from hipdwc import _lib, host, ops, penalty, synth          # noqa: E402
 
 T = torch.from_numpy
@@ -189,30 +190,16 @@ def fixture_penalties(golden_dir):
     return np.load(os.path.join(golden_dir, "tiny_penalties.npz"))
 
 
-def _tiny_solver(tiny, norm=None):
-    from solver import Solver
+def _config(norm=None, **top):
     cfg = synth.make_config(image_size=32, tiny=True)
     if norm is not None:
         cfg["dis"]["norm"] = norm
-    torch.manual_seed(1234)
-    s = Solver(cfg, torch.device(DEV), None).to(DEV)
-    s.copy_nets()
-    batch = {k[len("batch/"):]: T(tiny[k]) for k in tiny.files if k.startswith("batch/")}
-    return s, cfg, {k: v.to(DEV) for k, v in batch.items()}
+    return dict(cfg, **top)
 
 
-def _dis_update(s, cfg, batch, iters=15):
-    grabbed = {}
-    real_step = s.dis_opt.step
-
-    def grab(*a, **k):
-        grabbed.update({n: p.grad.detach().clone() for n, p in s.dis.named_parameters() if p.grad is not None})
-        return real_step(*a, **k)
-    s.dis_opt.step = grab
-    s.dis_update(batch["x_real"], batch["c_src"], batch["c_trg"], batch["txt"], batch["txt_lens"], batch["label_src"],
-                 batch["label_trg"], cfg, iters)
+def _dis_step(s, tiny, cfg, iters=15):
+    s.dis_update(*ts.step_args(ts.batch_of(tiny, DEV), cfg, iters))
     torch.cuda.synchronize()
-    return grabbed
 
 
 def _conv2d_forbidden(*a, **k):
@@ -225,15 +212,14 @@ def test_tiny_dis_penalties_vs_reference_by_branch(tiny, fixture_penalties, hip,
     the torch branch."""
     ref = fixture_penalties
     monkeypatch.setattr(ops, "PENALTY_HIP", 1 if hip else 0)
-    host.set_noise(host.HostNoise())
-    try:
-        s, cfg, batch = _tiny_solver(tiny)
+    with ts.host_noise():
+        s = ts.build(_config(), DEV)
         assert torch.equal(torch.get_rng_state(), T(tiny["rng_state_after_init"]))
-        cfg = dict(cfg, gp_w=10.0, use_r1=True)
+        grabbed = ts.grab_dis(s)
         if hip:
             assert s.dis.penalty_hip_ok()
             monkeypatch.setattr(F, "conv2d", _conv2d_forbidden)
-        grabbed = _dis_update(s, cfg, batch)
+        _dis_step(s, tiny, _config(gp_w=10.0, use_r1=True))
         monkeypatch.undo()
         for k in ("loss_dis", "loss_dis_all", "loss_gp", "loss_r1"):
             got, want = float(getattr(s, k)), float(ref[k])
@@ -241,30 +227,23 @@ def test_tiny_dis_penalties_vs_reference_by_branch(tiny, fixture_penalties, hip,
             assert abs(got - want) <= 2e-4 * max(abs(want), 1e-12) + (2e-4 if k != "loss_r1" else 0.0), (k, got, want)
         assert set(grabbed) == {n for n, _ in s.dis.named_parameters()}
         for k, g in grabbed.items():
+            assert g is not None, k
             err = rel_err(g, T(ref["grad/" + k]))
             print("grad %s: rel err %.3e" % (k, err))
             assert err <= 2e-3, (k, err)
-    finally:
-        host.set_noise(host.DeviceNoise())
 
 
 def test_r1_penalty_is_fp32_under_bf16(tiny, fixture_penalties, monkeypatch):
     """loss_r1 depends only on x_real and D's fp32 parameters: the branch runs the fp32 entry points under bf16 activations too."""
     monkeypatch.setattr(ops, "PENALTY_HIP", 1)
-    host.set_noise(host.HostNoise())
-    ops.set_precision("bf16")
-    try:
-        s, cfg, batch = _tiny_solver(tiny)
-        cfg = dict(cfg, gp_w=0.0, use_r1=True)
+    with ts.host_noise(), ts.precision("bf16"):
+        s = ts.build(_config(), DEV)
         monkeypatch.setattr(F, "conv2d", _conv2d_forbidden)
-        _dis_update(s, cfg, batch)
+        _dis_step(s, tiny, _config(gp_w=0.0, use_r1=True))
         monkeypatch.undo()
         got, want = float(s.loss_r1), float(fixture_penalties["loss_r1"])
         print("loss_r1 (bf16 mode): %.8e want %.8e" % (got, want))
         assert abs(got - want) <= 2e-4 * abs(want), (got, want)
-    finally:
-        ops.set_precision("fp32")
-        host.set_noise(host.DeviceNoise())
 
 
 def test_spectral_norm_keeps_the_torch_branch(tiny, monkeypatch):
@@ -276,11 +255,10 @@ def test_spectral_norm_keeps_the_torch_branch(tiny, monkeypatch):
     def counting(*a, **k):
         calls.append(1)
         return real(*a, **k)
-    s, cfg, batch = _tiny_solver(tiny, norm="sn")
+    s = ts.build(_config("sn"), DEV)
     assert not s.dis.penalty_hip_ok()
-    cfg = dict(cfg, gp_w=10.0, use_r1=True)
     monkeypatch.setattr(F, "conv2d", counting)
-    _dis_update(s, cfg, batch)
+    _dis_step(s, tiny, _config("sn", gp_w=10.0, use_r1=True))
     monkeypatch.undo()
     assert calls, "the torch branch did not run"
     for k in ("loss_gp", "loss_r1", "loss_dis_all"):

@@ -19,6 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import tiny_solver as ts
 from hipdwc import host, ops, synth          # noqa: E402
 
 T = torch.from_numpy
@@ -215,34 +216,16 @@ def test_forward_src_scale0_torch_matches_the_recorded_penalties(golden_dir, nor
     assert abs(got_gp - want_gp) <= 2e-4 * abs(want_gp), (got_gp, want_gp)
 
 
-def _tiny_solver(norm, meta, gan_type=None):
-    from solver import Solver
+def _config(norm, gan_type=None, **top):
     cfg = synth.make_config(image_size=32, tiny=True)
     cfg["dis"]["norm"] = norm
     if gan_type is not None:
         cfg["dis"]["gan_type"] = gan_type
-    torch.manual_seed(meta["seed"])
-    s = Solver(cfg, torch.device(DEV), None).to(DEV)
-    s.copy_nets()
-    batch = synth.make_batch(meta["B"], meta["S"], seed=meta["batch_seed"])
-    return s, cfg, {k: v.to(DEV) for k, v in batch.items()}
+    return dict(cfg, **top)
 
 
-def _grab_dis(s):
-    grabbed = {}
-    real_step = s.dis_opt.step
-
-    def grab(*a, **k):
-        grabbed.clear()
-        grabbed.update({n: (None if p.grad is None else p.grad.detach().clone()) for n, p in s.dis.named_parameters()})
-        return real_step(*a, **k)
-    s.dis_opt.step = grab
-    return grabbed
-
-
-def _args(batch, cfg, it):
-    return (batch["x_real"], batch["c_src"], batch["c_trg"], batch["txt"], batch["txt_lens"], batch["label_src"], batch["label_trg"],
-            cfg, it)
+def _batch(meta):
+    return {k: v.to(DEV) for k, v in synth.make_batch(meta["B"], meta["S"], seed=meta["batch_seed"]).items()}
 
 
 _REAL_CONV2D = F.conv2d
@@ -260,16 +243,15 @@ def test_tiny_dis_penalties_norm_vs_reference_by_branch(golden_dir, norm, hip, m
     the torch branch."""
     ref, meta, _ = _fixture(golden_dir, norm)
     monkeypatch.setattr(ops, "PENALTY_HIP", 1 if hip else 0)
-    host.set_noise(host.HostNoise())
-    try:
-        s, cfg, batch = _tiny_solver(norm, meta)
+    with ts.host_noise():
+        s = ts.build(_config(norm), DEV, seed=meta["seed"])
+        batch = _batch(meta)
         assert torch.equal(torch.get_rng_state(), T(ref["rng_state_after_init"]))
-        cfg = dict(cfg, gp_w=10.0, use_r1=True)
-        grabbed = _grab_dis(s)
+        grabbed = ts.grab_dis(s)
         if hip:
             assert s.dis.penalty_hip_ok()
             monkeypatch.setattr(F, "conv2d", _conv2d_forbidden)
-        s.dis_update(*_args(batch, cfg, meta["iters"]))
+        s.dis_update(*ts.step_args(batch, _config(norm, gp_w=10.0, use_r1=True), meta["iters"]))
         torch.cuda.synchronize()
         monkeypatch.undo()
         for k in ("loss_dis", "loss_dis_all", "loss_gp", "loss_r1"):
@@ -287,8 +269,6 @@ def test_tiny_dis_penalties_norm_vs_reference_by_branch(golden_dir, norm, hip, m
             lim = _limit(ref, "grad/" + k, norm)
             print("grad %s: max err %.3e, limit %.3e" % (k, err, lim))
             assert err <= lim, (k, err, lim)
-    finally:
-        host.set_noise(host.DeviceNoise())
 
 
 @pytest.mark.gpu
@@ -297,54 +277,45 @@ def test_r1_penalty_norm_is_fp32_under_bf16(golden_dir, norm, monkeypatch):
     """loss_r1 depends only on x_real and D's fp32 parameters: the branch runs the fp32 entry points under bf16 activations too."""
     ref, meta, _ = _fixture(golden_dir, norm)
     monkeypatch.setattr(ops, "PENALTY_HIP", 1)
-    host.set_noise(host.HostNoise())
-    ops.set_precision("bf16")
-    try:
-        s, cfg, batch = _tiny_solver(norm, meta)
-        cfg = dict(cfg, gp_w=0.0, use_r1=True)
+    with ts.host_noise(), ts.precision("bf16"):
+        s = ts.build(_config(norm), DEV, seed=meta["seed"])
         monkeypatch.setattr(F, "conv2d", _conv2d_forbidden)
-        s.dis_update(*_args(batch, cfg, meta["iters"]))
+        s.dis_update(*ts.step_args(_batch(meta), _config(norm, gp_w=0.0, use_r1=True), meta["iters"]))
         torch.cuda.synchronize()
         monkeypatch.undo()
         got, want = float(s.loss_r1), float(ref["loss_r1"])
         print("%s loss_r1 (bf16 mode): %.8e want %.8e" % (norm, got, want))
         assert abs(got - want) <= 2e-4 * abs(want), (got, want)
-    finally:
-        ops.set_precision("fp32")
-        host.set_noise(host.DeviceNoise())
 
 
 def _wgan_ln_two_iterations(hip, monkeypatch):
     monkeypatch.setattr(ops, "PENALTY_HIP", 1 if hip else 0)
-    host.set_noise(host.HostNoise())
-    try:
-        s, cfg, batch = _tiny_solver("ln", {"seed": 1234, "B": 3, "S": 32, "batch_seed": 4321}, gan_type="wgan")
-        cfg = dict(cfg, gp_w=10.0)
+    with ts.host_noise():
+        s = ts.build(_config("ln", gan_type="wgan"), DEV)
+        batch = _batch({"B": 3, "S": 32, "batch_seed": 4321})
+        cfg = _config("ln", gan_type="wgan", gp_w=10.0)
         # (the wgan objective does not depend on a constant added to src: the true gradient of the src heads' biases is zero, what is
         # computed for them is rounding noise, and Adam turns the SIGN of that noise into a step of lr -- frozen, as in
         # tests/golden/make_golden_gan.py and tests/test_gan_solver.py)
         for conv in s.dis.cnns_src:
             conv.bias.requires_grad_(False)
         assert s.dis.penalty_hip_ok()
-        grabbed = _grab_dis(s)
+        grabbed = ts.grab_dis(s)
         out = []
         for it in range(2):
             if hip:
                 monkeypatch.setattr(F, "conv2d", _conv2d_forbidden)
-            s.dis_update(*_args(batch, cfg, it))
+            s.dis_update(*ts.step_args(batch, cfg, it))
             if hip:
                 monkeypatch.setattr(F, "conv2d", _REAL_CONV2D)
-            s.gen_update(*_args(batch, cfg, it))
+            s.gen_update(*ts.step_args(batch, cfg, it))
             s.smooth_moving()
             s.update_learning_rate()
             s.update_attention_status(it)
             torch.cuda.synchronize()
-            losses = {k: float(torch.as_tensor(getattr(s, k)).detach())
-                      for k in ("loss_dis", "loss_dis_all", "loss_gp", "loss_gen_adv", "loss_gen_total")}
+            losses = ts.read_losses(s, ("loss_dis", "loss_dis_all", "loss_gp", "loss_gen_adv", "loss_gen_total"))
             out.append((losses, {k: (None if g is None else g.cpu()) for k, g in grabbed.items()}))
         return out
-    finally:
-        host.set_noise(host.DeviceNoise())
 
 
 @pytest.mark.gpu

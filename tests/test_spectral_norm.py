@@ -5,14 +5,14 @@ state_dict loads strictly.  GPU: the multi-tensor power iteration against a floa
 block against the imported reference (fixtures: tests/golden/make_golden_sn.py), fp32 and bf16, one segmented call = S calls; the
 tiny SN Solver over two iterations and a penalised D step against the reference."""
 import copy
-import json
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from hipdwc import host, ops, synth
+import tiny_solver as ts
+from hipdwc import ops, synth
 
 T = torch.from_numpy
 DEV = "cuda:0"
@@ -33,16 +33,6 @@ def _sn_config():
     return cfg
 
 
-def _build(cfg, device="cpu"):
-    from solver import Solver
-    torch.manual_seed(1234)
-    s = Solver(cfg, torch.device(device), None)
-    if device != "cpu":
-        s = s.to(device)
-    s.copy_nets()
-    return s
-
-
 def close(a, b, rel, atol=1e-6, msg=""):
     a, b = a.detach().float().cpu(), b.detach().float().cpu()
     assert a.shape == b.shape, (msg, a.shape, b.shape)
@@ -56,7 +46,7 @@ def close(a, b, rel, atol=1e-6, msg=""):
 # ---------------------------------------------------------------------------------------------------------------------------------
 def test_tiny_sn_init_equals_reference(golden_dir):
     ref = np.load(os.path.join(golden_dir, "tiny_sn_init.npz"))
-    s = _build(_sn_config())
+    s = ts.build(_sn_config())
     for prefix, mod in (("init/gen/", s.gen), ("init/dis/", s.dis)):
         sd = mod.state_dict()
         want = {k[len(prefix):]: ref[k] for k in ref.files if k.startswith(prefix)}
@@ -75,7 +65,7 @@ def test_tiny_sn_init_equals_reference(golden_dir):
     assert not any(id(p) in in_opt for p in uv)
     assert all(id(p) in in_opt for n, p in s.dis.named_parameters() if n.endswith("weight_bar"))
     # a reference SN checkpoint loads strictly
-    fresh = _build(_sn_config())
+    fresh = ts.build(_sn_config())
     fresh.dis.load_state_dict({k[len("init/dis/"):]: T(ref[k]) for k in ref.files if k.startswith("init/dis/")}, strict=True)
 
 
@@ -253,78 +243,41 @@ def _uv(s):
     return {k: v for k, v in s.dis.state_dict().items() if k.endswith("weight_u") or k.endswith("weight_v")}
 
 
-def _grab_dis(s):
-    grabbed = {}
-    real_step = s.dis_opt.step
-
-    def grab(*a, **k):
-        grabbed.update({n: p.grad.detach().clone() for n, p in s.dis.named_parameters() if p.grad is not None})
-        return real_step(*a, **k)
-    s.dis_opt.step = grab
-    return grabbed
-
-
 @pytest.mark.gpu
 def test_tiny_sn_two_iterations_vs_reference(golden_dir):
     """dis.norm 'sn': two iterations of the tiny Solver (HostNoise, the reference's random stream) against the imported reference:
-    every loss scalar, every D gradient of both D steps, every u / v after each dis_update (4 iterations per SN layer) and each
-    gen_update (2 more).  A wrong iteration count per step moves u / v by far more than the tolerance."""
-    ref = np.load(os.path.join(golden_dir, "tiny_sn_step.npz"))
-    want = json.loads(bytes(ref["losses_json"]).decode())
-    host.set_noise(host.HostNoise())
-    try:
-        cfg = _sn_config()
-        s = _build(cfg, DEV)
-        assert torch.equal(torch.get_rng_state(), T(ref["rng_state_after_init"]))
-        batch = {k[len("batch/"):]: T(ref[k]).to(DEV) for k in ref.files if k.startswith("batch/")}
-        grabbed = _grab_dis(s)
-        for it in range(2):
-            a = (batch["x_real"], batch["c_src"], batch["c_trg"], batch["txt"], batch["txt_lens"], batch["label_src"],
-                 batch["label_trg"], cfg, it)
-            grabbed.clear()
-            s.dis_update(*a)
-            uv_tol = 1e-5 if it == 0 else 1e-4         # (after iteration 0 Adam's sign steps may flip near-zero entries of W_bar)
-            for k, v in _uv(s).items():
-                close(v, T(ref["it%d/after_dis/%s" % (it, k)]), rel=0, atol=uv_tol, msg="it%d after_dis %s" % (it, k))
-            ref_g = {k[len("it%d/dgrad/" % it):]: T(ref[k]) for k in ref.files if k.startswith("it%d/dgrad/" % it)}
-            assert set(ref_g) == set(grabbed)
-            for k, g in ref_g.items():
-                close(grabbed[k], g, rel=2e-3 if it == 0 else 2e-2, msg="it%d dgrad %s" % (it, k))
-            s.gen_update(*a)
-            for k, v in _uv(s).items():
-                close(v, T(ref["it%d/after_gen/%s" % (it, k)]), rel=0, atol=1e-4, msg="it%d after_gen %s" % (it, k))
-            s.smooth_moving()
-            s.update_learning_rate()
-            s.update_attention_status(it)
-            tol = (2e-4, 5e-3)[it]
-            for k, v in want[it].items():
-                got = float(torch.as_tensor(getattr(s, k)).detach())
-                assert abs(got - v) <= tol * max(1.0, abs(v)), (it, k, got, v)
-    finally:
-        host.set_noise(host.DeviceNoise())
+    every loss scalar, every D gradient of both D steps (exactly the recorded parameters have one), every u / v after each
+    dis_update (4 iterations per SN layer) and each gen_update (2 more).  A wrong iteration count per step moves u / v by far more
+    than the tolerance."""
+    fx = ts.load(golden_dir, "tiny_sn_step")
+
+    def check_uv(it, s, when, atol):
+        for k, v in _uv(s).items():
+            close(v, T(fx.npz["it%d/after_%s/%s" % (it, when, k)]), rel=0, atol=atol, msg="it%d after_%s %s" % (it, when, k))
+
+    ts.two_iterations(fx, _sn_config(), ts.FIXED_BOUNDS._replace(frozen="rest"), init=False,      # (tiny_sn_init.npz holds the tensors)
+                      # (after iteration 0 Adam's sign steps may flip near-zero entries of W_bar)
+                      after_dis=lambda it, s: check_uv(it, s, "dis", 1e-5 if it == 0 else 1e-4),
+                      after_gen=lambda it, s: check_uv(it, s, "gen", 1e-4))
 
 
 @pytest.mark.gpu
 def test_tiny_sn_dis_penalties_vs_reference(golden_dir):
     """dis.norm 'sn' with gp_w = 10 and use_r1 (iteration 15): the penalties' scale-0 calls run one more iteration each, then
     W_bar / sigma in torch for the double backward; scalars, every D gradient and u / v against the reference."""
-    ref = np.load(os.path.join(golden_dir, "tiny_sn_step.npz"))
-    host.set_noise(host.HostNoise())
-    try:
+    fx = ts.load(golden_dir, "tiny_sn_step")
+    ref = fx.npz
+    with ts.host_noise():
         cfg = dict(_sn_config(), gp_w=10.0, use_r1=True)
-        s = _build(cfg, DEV)
-        batch = {k[len("batch/"):]: T(ref[k]).to(DEV) for k in ref.files if k.startswith("batch/")}
-        grabbed = _grab_dis(s)
-        s.dis_update(batch["x_real"], batch["c_src"], batch["c_trg"], batch["txt"], batch["txt_lens"], batch["label_src"],
-                     batch["label_trg"], cfg, 15)
+        s = ts.build(cfg, DEV)
+        grabbed = ts.grab_dis(s)
+        s.dis_update(*ts.step_args(fx.batch(DEV), cfg, 15))
         for k in ("loss_dis", "loss_dis_all", "loss_gp", "loss_r1"):
             got, want = float(getattr(s, k)), float(ref["pen/" + k])
             assert abs(got - want) <= 2e-4 * max(abs(want), 1e-12) + (2e-4 if k != "loss_r1" else 0.0), (k, got, want)
         ref_g = {k[len("pen/dgrad/"):]: T(ref[k]) for k in ref.files if k.startswith("pen/dgrad/")}
-        assert set(ref_g) == set(grabbed)
+        assert set(ref_g) == {k for k, g in grabbed.items() if g is not None}
         for k, g in ref_g.items():
             close(grabbed[k], g, rel=2e-3, msg=k)
         for k, v in _uv(s).items():
             close(v, T(ref["pen/after_dis/" + k]), rel=0, atol=1e-5, msg="pen after_dis " + k)
-    finally:
-        host.set_noise(host.DeviceNoise())
