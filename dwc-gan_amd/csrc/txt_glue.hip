@@ -211,6 +211,77 @@ __global__ __launch_bounds__(256) void txt_inter_bwd_kernel(const float* __restr
     }
 }
 
+// Regrouping feat (TxtEncoder's `group` / `sync`).  feat:[B][4LH] read flat is [2L planes][B] rows of 2H floats -- plane 2l + is_c,
+// caller sample b (txt_feat_at) --, and the feature row of a sample is 2L CONSECUTIVE flat rows: the reference's view(B, -1) over
+// the whole call.  Taking that view over another set of samples is a permutation of the rows.  The four forms give the source row
+// of destination row `o`; n counts rows inside the set the view is taken over:
+//   group fwd  (a = B,  b = G)  out row o = i*2L + k of sample i, group g = i / G:   n = o - g*G*2L  <- feat row (n/G)*B + g*G + n%G
+//   group bwd  (a = B,  b = G)  d_feat row o = p*B + g*G + rr:                       <- d_out row g*G*2L + p*G + rr
+//   rank fwd   (a = Bl, b = W)  out row o of rank r, n = r*Bl*2L + o, Bg = W*Bl:     <- rank (n%Bg)/Bl's feat row (n/Bg)*Bl + n%Bg%Bl
+//   rank bwd   (a = Bl, b = W)  d_feat row o = p*Bl + i2 of rank r:                  <- row p*Bg + r*Bl + i2 of the gathered d_out
+// Every source row lies inside its buffer for a, b >= 1 and b | a (group) or 0 <= r < b (rank): the host checks exactly that.
+enum { TXT_GROUP_FWD = 0, TXT_GROUP_BWD = 1, TXT_RANK_FWD = 2, TXT_RANK_BWD = 3 };
+
+__device__ __forceinline__ int txt_regroup_src(int form, int o, int L2, int a, int b, int r) {
+    if (form == TXT_GROUP_FWD) {
+        const int g = o / L2 / b, n = o - g * b * L2;
+        return (n / b) * a + g * b + n % b;
+    }
+    if (form == TXT_GROUP_BWD) {
+        const int p = o / a, s = o - p * a, g = s / b;
+        return g * b * L2 + p * b + (s - g * b);
+    }
+    if (form == TXT_RANK_FWD) {
+        const int Bg = a * b, n = r * a * L2 + o, p = n / Bg, row = n - p * Bg, s = row / a;
+        return s * a * L2 + p * a + (row - s * a);
+    }
+    const int p = o / a;
+    return p * a * b + r * a + (o - p * a);
+}
+
+// One block per destination row, 256 threads; VEC: 2H % 4 == 0 and both bases 16-byte aligned, the row moves as 16-byte words.
+template <bool VEC>
+__global__ __launch_bounds__(256) void txt_regroup_kernel(const float* __restrict__ src, float* __restrict__ dst, int form, int L2,
+                                                          int a, int b, int r, int width) {
+    const int o = blockIdx.x;
+    const size_t from = (size_t)txt_regroup_src(form, o, L2, a, b, r) * width, to = (size_t)o * width;
+    if (VEC) {
+        typedef float v4f __attribute__((ext_vector_type(4)));
+        const v4f* s = reinterpret_cast<const v4f*>(src + from);
+        v4f* d = reinterpret_cast<v4f*>(dst + to);
+        for (int k = threadIdx.x; k < width / 4; k += 256) d[k] = s[k];
+    } else {
+        for (int k = threadIdx.x; k < width; k += 256) dst[to + k] = src[from + k];
+    }
+}
+
+// rows: destination rows (one block each); rows_src: rows of the source buffer.  Both must fit a grid, and the larger buffer's last
+// 16-byte word an unsigned 32-bit index.
+int txt_regroup_launch(const float* src, float* dst, int form, int L, int a, int b, int r, int H, long long rows, long long rows_src,
+                       void* stream) {
+    if (rows < 1 || rows > 0x7fffffffLL || rows_src > 0x7fffffffLL) return DWC_EINVAL;
+    const unsigned long long width = 2ull * (unsigned)H;
+    if ((unsigned long long)(rows_src > rows ? rows_src : rows) * width > 4ull * 0xffffffffull) return DWC_EINVAL;
+    const bool vec = width % 4 == 0 && ((uintptr_t)src | (uintptr_t)dst) % 16 == 0;
+    if (vec)
+        hipLaunchKernelGGL(txt_regroup_kernel<true>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, src, dst, form, 2 * L, a, b,
+                           r, (int)width);
+    else
+        hipLaunchKernelGGL(txt_regroup_kernel<false>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, src, dst, form, 2 * L, a,
+                           b, r, (int)width);
+    DWC_LAUNCH_CHECK();
+    return DWC_OK;
+}
+
+bool txt_group_ok(const float* src, const float* dst, int L, int B, int H, int G) {
+    return src && dst && L >= 1 && L <= DWC_TXT_MAX_LAYERS && B >= 1 && H >= 1 && H <= 0x3fffffff && G >= 1 && B % G == 0;
+}
+
+bool txt_rank_ok(const float* src, const float* dst, int L, int W, int Bl, int H, int rank) {
+    return src && dst && L >= 1 && L <= DWC_TXT_MAX_LAYERS && W >= 1 && Bl >= 1 && H >= 1 && H <= 0x3fffffff && rank >= 0 && rank < W &&
+           (long long)W * Bl <= 0x7fffffffLL;
+}
+
 bool txt_layers_ok(const dwc_txt_layers& ly) { return ly.n >= 1 && ly.n <= DWC_TXT_MAX_LAYERS; }
 
 }  // namespace
@@ -303,6 +374,26 @@ int dwc_txt_states_bwd(const float* d_feat, const int* order, const int* last, d
                        T, B, H);
     DWC_LAUNCH_CHECK();
     return DWC_OK;
+}
+
+int dwc_txt_regroup_fwd(const float* feat, float* out, int L, int B, int H, int G, void* stream) {
+    if (!txt_group_ok(feat, out, L, B, H, G)) return DWC_EINVAL;
+    return txt_regroup_launch(feat, out, TXT_GROUP_FWD, L, B, G, 0, H, 2LL * L * B, 2LL * L * B, stream);
+}
+
+int dwc_txt_regroup_bwd(const float* d_out, float* d_feat, int L, int B, int H, int G, void* stream) {
+    if (!txt_group_ok(d_out, d_feat, L, B, H, G)) return DWC_EINVAL;
+    return txt_regroup_launch(d_out, d_feat, TXT_GROUP_BWD, L, B, G, 0, H, 2LL * L * B, 2LL * L * B, stream);
+}
+
+int dwc_txt_regroup_rank_fwd(const float* feat_all, float* out, int L, int W, int Bl, int H, int rank, void* stream) {
+    if (!txt_rank_ok(feat_all, out, L, W, Bl, H, rank)) return DWC_EINVAL;
+    return txt_regroup_launch(feat_all, out, TXT_RANK_FWD, L, Bl, W, rank, H, 2LL * L * Bl, 2LL * L * Bl * W, stream);
+}
+
+int dwc_txt_regroup_rank_bwd(const float* d_out_all, float* d_feat, int L, int W, int Bl, int H, int rank, void* stream) {
+    if (!txt_rank_ok(d_out_all, d_feat, L, W, Bl, H, rank)) return DWC_EINVAL;
+    return txt_regroup_launch(d_out_all, d_feat, TXT_RANK_BWD, L, Bl, W, rank, H, 2LL * L * Bl, 2LL * L * Bl * W, stream);
 }
 
 }  // extern "C"

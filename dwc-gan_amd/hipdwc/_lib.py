@@ -279,6 +279,11 @@ SIGNATURES = {
     # ---- the layer-1 operand from dense word embeddings (TxtEncoder.forward_embed; additive in ABI 11) ----
     "dwc_txt_operand_embed_fwd": (c_int, [c_fp] * 6 + [c_int] * 5 + [c_fp]),
     "dwc_txt_operand_embed_bwd": (c_int, [c_fp] * 7 + [c_int] * 5 + [c_fp]),
+    # ---- regrouping the feature buffer: groups of G, or W ranks of Bl samples (hipdwc.txt.regroup; additive in ABI 11) ----
+    "dwc_txt_regroup_fwd": (c_int, [c_fp, c_fp] + [c_int] * 4 + [c_fp]),
+    "dwc_txt_regroup_bwd": (c_int, [c_fp, c_fp] + [c_int] * 4 + [c_fp]),
+    "dwc_txt_regroup_rank_fwd": (c_int, [c_fp, c_fp] + [c_int] * 5 + [c_fp]),
+    "dwc_txt_regroup_rank_bwd": (c_int, [c_fp, c_fp] + [c_int] * 5 + [c_fp]),
     # ---- uint8 HWC crops to the internal image buffer (hipdwc.u8image; additive in ABI 11) ----
     "dwc_image_u8_ksize": (c_int, [c_int, c_int]),
     "dwc_image_u8_ws_bytes": (c_sz, [c_int] * 6),

@@ -169,6 +169,117 @@ def states_bwd(d_feat, order, last, T, H, need_out):
     return d_outs, d_cs
 
 
+def group_rows(layers, B, G):
+    """Source flat row (of 2H floats) of every output row of ``regroup`` in groups of G: int64 [2*layers*B]."""
+    L2 = 2 * layers
+    o = torch.arange(L2 * B, dtype=torch.int64)
+    g = o // L2 // G
+    n = o - g * G * L2
+    return (n // G) * B + g * G + n % G
+
+
+def rank_rows(layers, W, Bl, rank):
+    """(fwd, bwd): the row of the gathered [W][Bl][2*layers] rows that each output row of rank ``rank`` is, and the row of the gathered
+    output gradients that each flat row of its own feat gradient is; int64 [2*layers*Bl] each."""
+    L2, Bg = 2 * layers, W * Bl
+    o = torch.arange(L2 * Bl, dtype=torch.int64)
+    n = rank * Bl * L2 + o
+    p, row = n // Bg, n % Bg
+    s = row // Bl
+    return s * Bl * L2 + p * Bl + row % Bl, (o // Bl) * Bg + rank * Bl + o % Bl
+
+
+def _gathered(sync, t):
+    out = sync.all_gather(t)
+    if tuple(out.shape) != (sync.world,) + tuple(t.shape) or out.dtype != t.dtype or out.device != t.device:
+        raise ValueError("regroup: sync.all_gather returned %s %s, expected %s" % (tuple(out.shape), out.dtype,
+                                                                                   (sync.world,) + tuple(t.shape)))
+    return out.contiguous()
+
+
+class _Regroup(torch.autograd.Function):
+    """feat [B, 4LH] -> the feature rows of the view taken per group of G samples (``sync`` None) or over the union of ``sync``'s
+    ranks, on dwc_txt_regroup_*: one launch each way, and one all-gather each way in the rank form."""
+
+    @staticmethod
+    def forward(ctx, feat, L, G, sync):
+        B, F = _f32(feat).shape
+        H = F // (4 * L)
+        ctx.geom, ctx.sync = (L, B, H, G), sync
+        out = torch.empty((B, F), dtype=torch.float32, device=feat.device)
+        lib = _lib.load()
+        if sync is None:
+            _lib.check(lib.dwc_txt_regroup_fwd(feat.data_ptr(), out.data_ptr(), L, B, H, G, _stream()), "txt_regroup_fwd")
+        else:
+            every = _gathered(sync, feat)
+            _lib.check(lib.dwc_txt_regroup_rank_fwd(every.data_ptr(), out.data_ptr(), L, sync.world, B, H, sync.rank, _stream()),
+                       "txt_regroup_rank_fwd")
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        (L, B, H, G), sync = ctx.geom, ctx.sync
+        d_out = _f32(d_out.contiguous())
+        d_feat = torch.empty((B, 4 * L * H), dtype=torch.float32, device=d_out.device)
+        lib = _lib.load()
+        if sync is None:
+            _lib.check(lib.dwc_txt_regroup_bwd(d_out.data_ptr(), d_feat.data_ptr(), L, B, H, G, _stream()), "txt_regroup_bwd")
+        else:
+            every = _gathered(sync, d_out)
+            _lib.check(lib.dwc_txt_regroup_rank_bwd(every.data_ptr(), d_feat.data_ptr(), L, sync.world, B, H, sync.rank, _stream()),
+                       "txt_regroup_rank_bwd")
+        return d_feat, None, None, None
+
+
+class _RegroupTorch(torch.autograd.Function):
+    """The same permutation as stock indexing, in feat's precision and on its device: the A/B partner."""
+
+    @staticmethod
+    def forward(ctx, feat, L, G, sync):
+        B, F = feat.shape
+        ctx.shape, ctx.sync = (B, F, F // (2 * L)), sync
+        if sync is None:
+            fwd = group_rows(L, B, G)
+            ctx.bwd = torch.sort(fwd)[1]                    # (the inverse permutation)
+            src = feat
+        else:
+            fwd, ctx.bwd = rank_rows(L, sync.world, B, sync.rank)
+            src = _gathered(sync, feat.contiguous())
+        return src.reshape(-1, ctx.shape[2]).index_select(0, fwd.to(feat.device)).reshape(B, F)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        B, F, width = ctx.shape
+        src = d_out if ctx.sync is None else _gathered(ctx.sync, d_out.contiguous())
+        return src.reshape(-1, width).index_select(0, ctx.bwd.to(d_out.device)).reshape(B, F), None, None, None
+
+
+def regroup(feat, group=None, sync=None, layers=None):
+    """The heads' feature rows of ``feat`` [B, 4*layers*H] (``states_fwd``: the reference's view over the whole call) with the view
+    taken over other sets of samples: per ``group`` consecutive samples -- 1: every row is the one of a batch-1 call --,
+    or, with an active ``sync`` (``world``, ``rank``, ``all_gather``; hipdwc.syncbn.active), over the union of the ranks' batches in
+    rank order, which gives this rank its rows of the single-device call on the concatenated batch.  ``group`` None or B without an
+    active ``sync`` returns ``feat`` itself.  On the device with ``ops.TXT_FUSED`` the kernels move the rows; elsewhere stock indexing."""
+    from .syncbn import active
+    if feat.dim() != 2:
+        raise ValueError("regroup: feat must be [batch, 4 * layers * hidden], got %s" % (list(feat.shape),))
+    B, F = feat.shape
+    on = active(sync)
+    if group is not None and (int(group) < 1 or B % int(group)):
+        raise ValueError("regroup: group %s does not divide the batch of %d" % (group, B))
+    if group is not None and on:
+        raise ValueError("regroup: group and an active sync exclude each other (the view is taken over the ranks' union)")
+    if not on and (group is None or int(group) == B):
+        return feat
+    if layers is None or layers < 1 or F % (4 * layers):
+        raise ValueError("regroup: %s layers do not divide a feature row of %d" % (layers, F))
+    if feat.is_cuda and ops.TXT_FUSED:
+        if layers > MAX_LAYERS:
+            raise ValueError("the text encoder's kernels take up to %d LSTM layers (DWC_TXT_MAX_LAYERS), got %d" % (MAX_LAYERS, layers))
+        return _Regroup.apply(feat.contiguous(), int(layers), 0 if on else int(group), sync if on else None)
+    return _RegroupTorch.apply(feat, int(layers), 0 if on else int(group), sync if on else None)
+
+
 class _Plan:
     """What one call of ``encode`` fixes outside the differentiable inputs: indices, masks, sizes, cache owners."""
     __slots__ = ("dense", "tokens", "order", "unsort", "lens", "last", "t_max", "mask_in", "masks", "mask_rows", "owners_ih", "owners_hh", "owners_b",

@@ -120,8 +120,12 @@ class TxtEncoder(nn.Module):
     """Command text + current style -> per-attribute (mu, logvar) (reference networks_v2.py:171-254)."""
 
     def __init__(self, vocab, embed_dim=512, hidden_size=512, c_dim=8, num_class=8, num_layers=1, dropout_in=0.1,
-                 dropout_out=0.1, bidirectional=True, pretrained_embed=None):
+                 dropout_out=0.1, bidirectional=True, pretrained_embed=None, group=None):
         super().__init__()
+        # over which samples the heads' feature rows are formed (hipdwc.txt.regroup; not in the state_dict): ``group`` None / 0 = the
+        # whole call, as the reference; G = consecutive groups of G samples (1: every sample as a batch-1 call).  ``sync``: an object
+        # of hipdwc.syncbn under data parallel (Solver.enable_data_parallel(sync_txt=True)): the union of the ranks' batches.
+        self.group, self.sync = group, None
         self.vocab, self.embed_dim, self.hidden_size = vocab, embed_dim, hidden_size
         self.num_layers, self.dropout_in, self.dropout_out = num_layers, dropout_in, dropout_out
         self.bidirectional, self.num_class, self.style_dim = bidirectional, num_class, c_dim * num_class
@@ -141,18 +145,23 @@ class TxtEncoder(nn.Module):
             self.fcs.append(nn.Linear(feat, c_dim))
             self.fcvars.append(nn.Linear(feat, c_dim))
 
-    def forward(self, style_ord, src_tokens, src_lengths):
+    def forward(self, style_ord, src_tokens, src_lengths, group=None):
+        """``group`` (None: the module's ``group``): see ``__init__``; the random draws are those of the ungrouped call."""
         if not self.bidirectional:
             raise NotImplementedError("the HIP text encoder is bidirectional (the reference's only configuration)")
         if ops.TXT_FUSED and src_tokens.is_cuda:
             # everything up to the heads' feature row on the kernels of csrc/txt_glue.hip: one launch per tensor built here
-            return self._heads(txt.encode(self, style_ord, src_tokens, src_lengths, _packed_index))
+            return self._heads(self._regroup(txt.encode(self, style_ord, src_tokens, src_lengths, _packed_index), group))
         # DWC_TXT_FUSED=0: the same computation as stock tensor ops (the reference of tests/test_txt_fused.py)
         tokens = src_tokens.transpose(1, 0)
         return self._stock(style_ord, src_lengths, tokens.shape[0], tokens.shape[1], tokens.device,
-                           lambda order, lens_dev: self.embed_tokens(tokens.index_select(1, order)))
+                           lambda order, lens_dev: self.embed_tokens(tokens.index_select(1, order)), group)
 
-    def forward_embed(self, style_ord, embeddings, lengths):
+    def _regroup(self, feat, group):
+        group = self.group if group is None else group
+        return txt.regroup(feat, group or None, self.sync, layers=self.num_layers)
+
+    def forward_embed(self, style_ord, embeddings, lengths, group=None):
         """``forward`` with the table lookup replaced by the caller's word vectors (reference networks_v2.py:256-293): ``embeddings``
         [B, seq_len, embed_dim], ``lengths`` a tensor on any device or a list.  The reference takes lengths in decreasing order only;
         any order is sorted here as ``forward`` does.  What lies behind a sample's length is never read (NaN and Inf included) and
@@ -171,16 +180,17 @@ class TxtEncoder(nn.Module):
         if not self.bidirectional:
             raise NotImplementedError("the HIP text encoder is bidirectional (the reference's only configuration)")
         if ops.TXT_FUSED and embeddings.is_cuda:
-            return self._heads(txt.encode(self, style_ord, None, lens_host, _packed_index, embeddings=embeddings.float().contiguous()))
+            return self._heads(self._regroup(txt.encode(self, style_ord, None, lens_host, _packed_index,
+                                                        embeddings=embeddings.float().contiguous()), group))
         # DWC_TXT_FUSED=0: the stock-tensor-op expression (the A/B partner of tests/test_txt_embed.py)
         steps = torch.arange(seq_len, device=embeddings.device).view(-1, 1, 1)
 
         def embed(order, lens_dev):
             x = embeddings.float().transpose(0, 1).index_select(1, order)
             return torch.where(steps < lens_dev.view(1, -1, 1), x, torch.zeros((), dtype=x.dtype, device=x.device))
-        return self._stock(style_ord, lens_host, seq_len, bsz, embeddings.device, embed)
+        return self._stock(style_ord, lens_host, seq_len, bsz, embeddings.device, embed, group)
 
-    def _stock(self, style_ord, src_lengths, seq_len, bsz, dev, embed):
+    def _stock(self, style_ord, src_lengths, seq_len, bsz, dev, embed, group=None):
         """Everything of ``forward`` / ``forward_embed`` as stock tensor ops around ``ops.lstm_bidir``.  ``embed(order, lens_dev)``:
         the embedded words [seq_len, B, E] in length-sorted order, before dropout_in."""
         noise = host.noise()
@@ -238,7 +248,7 @@ class TxtEncoder(nn.Module):
         h_n, c_n = _Permute.apply(h_n, 1, unsort, order), _Permute.apply(c_n, 1, unsort, order)
         # reference networks_v2.py:249: concatenating along the BATCH axis and then viewing as
         # (batch, -1) interleaves samples of the local batch; reproduced, not fixed
-        return self._heads(torch.cat([h_n, c_n], dim=1).view(bsz, -1))
+        return self._heads(self._regroup(torch.cat([h_n, c_n], dim=1).view(bsz, -1), group))
 
     def _heads(self, feat):
         # the 2*num_class heads read the same feature row: one [2*num_class*c_dim, feat] product
@@ -268,7 +278,8 @@ class AdaINGen_v2(nn.Module):
                            res_norm="adain", activ=p["activ"], pad_type=p["pad_type"],
                            use_attention=p["use_attention"])
         self.enc_txt = TxtEncoder(vocab, p["embed_dim"], p["hidden_size"], p["c_dim"], p["num_cls"], p["num_layers"],
-                                  p["dropout_in"], p["dropout_out"], pretrained_embed=pretrained_embed)
+                                  p["dropout_in"], p["dropout_out"], pretrained_embed=pretrained_embed,
+                                  group=p.get("txt_group") or None)      # (optional key gen.txt_group; absent / None / 0: reference layout)
         self.mlp = MLP(style_dim, self.get_num_adain_params(self.dec), p["mlp_dim"], 3, norm="none", activ=p["activ"])
 
     # -- reference API -------------------------------------------------------------------
@@ -288,8 +299,8 @@ class AdaINGen_v2(nn.Module):
             return None
         return host.noise().dropout_mask((batch, es.mapping[0].out_features), es.mapping[2].p, device)
 
-    def encode_txt(self, style_ord, txt_org2trg, txt_lens):
-        return self.enc_txt(style_ord, txt_org2trg, txt_lens)
+    def encode_txt(self, style_ord, txt_org2trg, txt_lens, group=None):
+        return self.enc_txt(style_ord, txt_org2trg, txt_lens, group=group)
 
     def decode(self, content, style):
         self.assign_adain_params(self.mlp(style), self.dec)

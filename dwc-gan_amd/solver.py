@@ -106,12 +106,15 @@ class Solver(nn.Module):
                 param.requires_grad = False
 
     # ---- data parallel -----------------------------------------------------------------------
-    def enable_data_parallel(self, group=None, bucket_bytes=DP_BUCKET_BYTES, sync_bn=None):
+    def enable_data_parallel(self, group=None, bucket_bytes=DP_BUCKET_BYTES, sync_bn=None, sync_txt=None):
         """One process per GPU (torch.distributed initialised by the caller, backend nccl = RCCL): gradients of D / G become
         views of flat buckets that are all-reduced (averaged) as backward completes them (hipdwc.dp.OverlappedGradReducer).
         ``sync_bn`` (None: the environment's DWC_SYNC_BN, default 0): the batch-norm layers of D (dis.norm 'bn') take their batch
         statistics over all ranks (hipdwc.syncbn: two small all-gathers per layer and pass on the same group); off, they stay per
-        rank and a warning says so."""
+        rank and a warning says so.
+        ``sync_txt`` (None: the environment's DWC_SYNC_TXT, default 0): the text encoder forms its feature rows over the union of the
+        ranks' batches (hipdwc.txt.regroup: one all-gather of the [B, 4LH] buffer per call and pass), which makes its function the
+        single-device one on the concatenated batch; off, every rank mixes inside its own shard.  Dropout draws stay per rank."""
         from hipdwc import dp, syncbn
         self._reducers = {"dis": dp.OverlappedGradReducer(self.dis_opt.param_groups[0]["params"], group, bucket_bytes),
                           "gen": dp.OverlappedGradReducer(self.gen_opt.param_groups[0]["params"], group, bucket_bytes)}
@@ -124,6 +127,12 @@ class Solver(nn.Module):
                 m.sync = syncbn.GroupSync(group, force=force)
         else:
             dp.warn_per_rank_batchnorm(self.dis.bn_layers(), group)
+        if sync_txt is None:
+            sync_txt = os.environ.get("DWC_SYNC_TXT", "0") == "1"
+        if sync_txt:
+            for g in (self.gen, getattr(self, "gen_test", None)):
+                if g is not None:
+                    g.enc_txt.sync = syncbn.GroupSync(group, force=force)
         # the persistent LSTM launches need ALL their workgroups resident while RCCL's all-reduce kernels (launched from inside
         # backward on a side stream) hold CUs of their own: keep those launches to half of a 256-CU device; larger grids take the
         # per-step kernels (dwc_lstm_seq_* return DWC_EINVAL above the cap)
@@ -232,10 +241,11 @@ class Solver(nn.Module):
             content, groups = torch.cat([content] * groups), 1
         return self.gen.decode_nhwc4(content, style, attention_used=attention_used, groups=groups)
 
-    def forward(self, x_real, txt_src2trg, txt_lens):
+    def forward(self, x_real, txt_src2trg, txt_lens, txt_group=None):
+        """``txt_group`` (None: the text encoder's own ``group``): 1 gives every image the style of a batch-1 call."""
         x4 = ops.pack_image(x_real)
         content, style_src, _ = self.gen.encode(x4)
-        style_txt, _ = self.gen.encode_txt(flat_heads(style_src), txt_src2trg, txt_lens)
+        style_txt, _ = self.gen.encode_txt(flat_heads(style_src), txt_src2trg, txt_lens, group=txt_group)
         return self._decode(content, flat_heads(style_txt), x4)[:, :3].float()
 
     # ---- penalties (reference solver.py:291-315) --------------------------------------------------

@@ -960,6 +960,23 @@ int dwc_txt_states_fwd(dwc_txt_layers layers, const int* last, const int* unsort
 /* The adjoint: every non-NULL tensor of `grads` receives its rows of d_feat at the final-state slots and zeros everywhere else. */
 int dwc_txt_states_bwd(const float* d_feat, const int* order, const int* last, dwc_txt_layers grads, int T, int B, int H,
                        void* stream);
+/* Regrouping feat: over which samples the reference's view(B, -1) is taken (TxtEncoder group / sync; additive in ABI 11).
+ * feat:[B][4LH] read flat is [2L planes p = 2l + is_c][B] rows of 2H floats; a sample's feature row is 2L consecutive flat rows.
+ * Groups of G (G divides B): output row k (0 <= k < 2L) of sample i, with g = i / G, n = (i % G)*2L + k, is feat's flat row
+ *   (n / G)*B + g*G + n % G.     G == B: the identity; G == 1: every sample gets the row of a batch-1 call.
+ * The adjoint takes d_out:[B][4LH] and writes d_feat:[B][4LH], the inverse permutation.
+ * Pure movement: one launch, every output element written exactly once, no scratch, no atomics, no library state; rows move as
+ * 16-byte words when 2H % 4 == 0 and both pointers are 16-byte aligned.  DWC_EINVAL before any launch for a NULL pointer, L outside
+ * 1..DWC_TXT_MAX_LAYERS, B, H or G < 1, B % G != 0, more than 2^31-1 rows or more than 2^32-1 16-byte words in a buffer. */
+int dwc_txt_regroup_fwd(const float* feat, float* out, int L, int B, int H, int G, void* stream);
+int dwc_txt_regroup_bwd(const float* d_out, float* d_feat, int L, int B, int H, int G, void* stream);
+/* The same across W ranks of Bl samples.  feat_all:[W][Bl][4LH], the ranks' local feat buffers in rank order; out:[Bl][4LH] is for
+ * `rank`: with Bg = W*Bl and n = (rank*Bl + i)*2L + k, p = n / Bg, row = n % Bg, output row k of local sample i is rank
+ * (row / Bl)'s flat row p*Bl + row % Bl -- rows rank*Bl .. (rank+1)*Bl-1 of what one device computes on the concatenated batch.
+ * The adjoint takes d_out_all:[W][Bl][4LH], the ranks' output gradients in rank order, and writes d_feat:[Bl][4LH] of `rank`
+ * (flat row p*Bl + i2 is row p*Bg + rank*Bl + i2 of d_out_all).  Refusals as above, with W, Bl < 1 and rank outside 0..W-1. */
+int dwc_txt_regroup_rank_fwd(const float* feat_all, float* out, int L, int W, int Bl, int H, int rank, void* stream);
+int dwc_txt_regroup_rank_bwd(const float* d_out_all, float* d_feat, int L, int W, int Bl, int H, int rank, void* stream);
 
 /* ---- input pipeline: uint8 HWC crops to the internal image buffer (additive in ABI 11; csrc/image_u8.hip, DESIGN.md 25;
  *      reference data_loader.py:11-22, the Resize / ToTensor / Normalize steps of its transform chain) -----------------------------
