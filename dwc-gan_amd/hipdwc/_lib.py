@@ -28,6 +28,10 @@ BN_MAX_SEGMENTS = 8                            # DWC_BN_MAX_SEGMENTS
 TXT_MAX_LAYERS = 4                            # DWC_TXT_MAX_LAYERS
 
 
+IMAGE_OUT_MAX_SOURCES = 8                     # DWC_IMAGE_OUT_MAX_SOURCES
+IMAGE_OUT_LAYOUTS = {"nchw1": 0, "nchw3": 1, "nhwc4": 2, "nhwc8_bf16": 3}      # DWC_IMAGE_OUT_*
+
+
 class TxtLayers(ctypes.Structure):             # struct dwc_txt_layers (passed by value)
     _fields_ = [("n", c_int), ("out", c_fp * TXT_MAX_LAYERS), ("c", c_fp * TXT_MAX_LAYERS)]
 
@@ -289,6 +293,10 @@ SIGNATURES = {
     "dwc_image_u8_ws_bytes": (c_sz, [c_int] * 6),
     "dwc_image_u8_to_nhwc4": (c_int, [c_fp] * 7 + [c_int] * 6 + [c_fp, c_sz, c_fp]),
     "dwc_bf16_image_u8_to_nhwc8": (c_int, [c_fp] * 7 + [c_int] * 6 + [c_fp, c_sz, c_fp]),
+    # ---- image batches to one uint8 HWC grid (hipdwc.u8image.grid_u8 / image_to_u8; additive in ABI 11): the first four (three)
+    # arguments and value_range are HOST arrays ----
+    "dwc_image_out_ws_bytes": (c_sz, [c_fp] * 3 + [c_int] * 5),
+    "dwc_image_out_grid_u8": (c_int, [c_fp] * 4 + [c_int] * 4 + [c_fp, c_fp, c_fp, c_sz, c_fp]),
 }
 
 ABI_VERSION = 11             # DWC_ABI_VERSION of include/dwcgan_hip.h

@@ -241,12 +241,15 @@ class Solver(nn.Module):
             content, groups = torch.cat([content] * groups), 1
         return self.gen.decode_nhwc4(content, style, attention_used=attention_used, groups=groups)
 
-    def forward(self, x_real, txt_src2trg, txt_lens, txt_group=None):
-        """``txt_group`` (None: the text encoder's own ``group``): 1 gives every image the style of a batch-1 call."""
+    def forward(self, x_real, txt_src2trg, txt_lens, txt_group=None, internal=False):
+        """``txt_group`` (None: the text encoder's own ``group``): 1 gives every image the style of a batch-1 call.
+        ``internal``: return the decoder's internal image buffer (planes 0..2 are the image; what ``hipdwc.u8image.image_to_u8``
+        takes) instead of the fp32 NCHW image."""
         x4 = ops.pack_image(x_real)
         content, style_src, _ = self.gen.encode(x4)
         style_txt, _ = self.gen.encode_txt(flat_heads(style_src), txt_src2trg, txt_lens, group=txt_group)
-        return self._decode(content, flat_heads(style_txt), x4)[:, :3].float()
+        out = self._decode(content, flat_heads(style_txt), x4)
+        return out if internal else out[:, :3].float()
 
     # ---- penalties (reference solver.py:291-315) --------------------------------------------------
     def gradient_penalty(self, y, x):

@@ -1001,6 +1001,36 @@ int dwc_bf16_image_u8_to_nhwc8(const uint8_t* u8, const int* xstart, const int* 
                                const float* lut, void* y, int B, int Hin, int Win, int C, int Hout, int Wout, void* ws, size_t ws_bytes,
                                void* stream);
 
+/* ---- output pipeline: image batches to one uint8 HWC grid (additive in ABI 11; csrc/image_out_u8.hip; reference
+ *      utils.py:69-73, make_grid(nrow, padding 0, normalize) + save_image's byte conversion) ---------------------------------------
+ * K sources, 1..DWC_IMAGE_OUT_MAX_SOURCES, described by four HOST arrays of K entries that travel to the kernels by value:
+ *   src[k]     device pointer;  layout[k]  one of DWC_IMAGE_OUT_*;  batch[k]  images the buffer holds;  used[k]  the first used[k]
+ *              of them enter, 1..batch[k].  All sources are H x W.  Of an internal buffer planes 0..2 are read, nothing else; a
+ *              one-plane source gives all three channels.  Internal buffers must be 16-byte aligned, dense ones 4-byte aligned.
+ * The N = sum used[k] images, in source order, tile a grid of cols = min(nrow, N) columns and rows = ceil(N / cols) rows: image j
+ * sits in row j / cols, column j % cols; cells without an image are 0.  out:[rows*H][cols*W][3] uint8, every byte written.
+ * Each value goes through, every operation rounded to fp32 on its own (no fused multiply-add, a true division):
+ *   v = min(max(x, lo), hi);  v = v - lo;  v = v / d;  v = v * 255;  v = v + 0.5;  byte = (uint8) min(max(v, 0), 255)
+ * with d = (float) max((double) hi - (double) lo, 1e-5).  value_range: HOST pointer to {lo, hi}, or NULL: lo and hi are the minimum
+ * and maximum over exactly the values that enter (used images, planes 0..2), found by a first launch that leaves one (min, max)
+ * pair per workgroup in `ws`, at most DWC_IMAGE_OUT_MAX_PARTIALS of them; every workgroup of the second launch reduces them again
+ * (min and max are exact: no order dependence, no atomics, no host read-back).  With a value_range the call is one launch and
+ * needs no scratch.  Four neighbouring pixels leave as three aligned 32-bit stores where W % 4 == 0 and `out` is 4-byte aligned,
+ * single bytes otherwise.  Finite inputs are the contract: a NaN or infinity never moves an access, but its bytes (and, without a
+ * value_range, everyone's) are unspecified.
+ * DWC_EINVAL before any launch: a NULL src/layout/batch/used/out or src[k], K outside 1..DWC_IMAGE_OUT_MAX_SOURCES, H, W or nrow < 1,
+ * H or W > 16384, batch[k] < 1 or > 65535, used[k] < 1 or > batch[k], an unknown layout, a misaligned pointer.  DWC_EWORKSPACE: no
+ * value_range and less scratch than dwc_image_out_ws_bytes (which is 0 with a value_range and for whatever the call refuses). */
+#define DWC_IMAGE_OUT_MAX_SOURCES 8
+#define DWC_IMAGE_OUT_MAX_PARTIALS 256
+#define DWC_IMAGE_OUT_NCHW1 0       /* dense fp32 [B][1][H][W] */
+#define DWC_IMAGE_OUT_NCHW3 1       /* dense fp32 [B][3][H][W] */
+#define DWC_IMAGE_OUT_NHWC4 2       /* fp32 [B][H][W][4], internal image buffer */
+#define DWC_IMAGE_OUT_NHWC8_BF16 3  /* bf16 [B][H][W][8], internal image buffer */
+size_t dwc_image_out_ws_bytes(const int* layout, const int* batch, const int* used, int K, int H, int W, int nrow, int from_data);
+int dwc_image_out_grid_u8(const void* const* src, const int* layout, const int* batch, const int* used, int K, int H, int W, int nrow,
+                          const double* value_range, uint8_t* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
